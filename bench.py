@@ -20,9 +20,11 @@ the same volumes on the host cores (`cpu_baseline`).  Nested under "configs3": t
 `--instance-volumes V` / `--volumes V` run either leg alone with V volumes on any number of GPUs (N = 1: all time-sliced);
 `--replicas` runs N independent copies of configs[1] (no collective).
 
-Prints ONE JSON line on rank 0 (see the driver contract in the task statement) with the
-extra objects "roofline" (dominant kernel: integrate) and "cpu_baseline" (the CPU oracle on
-a bounded sample of the same workload).
+Prints ONE JSON line on rank 0.  A one-volume run (`--gpus 1`) measures its headline and nothing else: set-up (the frames are
+rendered on the device), warm-up, the --steps timed steps, --dump-outputs DIR if given; "roofline", "cpu_baseline",
+"through_shim" and "kernels" stay null / empty.  With --full the line also carries the objects "roofline" (dominant kernel:
+integrate), "cpu_baseline" (the CPU oracle on a bounded sample of the same workload), the C++-host legs, the scaling leg and
+the nested configs[2] / [3] / [4] legs.
 """
 import argparse
 import json
@@ -37,6 +39,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+AUX_STEPS, AUX_WARMUP = 45, 20  # bounds of the timed / warm-up steps of --full's legs other than the headline (45, 5: the defaults)
 SCALING_VOLUMES = 8   # north_star: "8 concurrent instance volumes" — the SAME workload at 1 / 2 / 4 / 8 GPUs (strong scaling)
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 HBM_GUIDE_COPY_GBS = 6290.0  # ... and the 6.29 TB/s its float4 copy kernel measures (79 %)
@@ -79,6 +82,118 @@ def make_frames(w, h, n, n_inst=0):
         return [_gen_frame((w, h, i, n_inst)) for i in range(n)]
     with Pool(procs) as pool:
         return pool.map(_gen_frame, [(w, h, i, n_inst) for i in range(n)])
+
+
+def device_frames(w, h, first, n, dev, batch=16, threads=16):
+    """Frames first .. first+n-1 of StreetScene(w, h) without moving boxes, rendered on `dev` in batches: -> [(rgba uint8 [H,W,4],
+    depth int16 mm [H,W]) device tensors], poses.  The same float64 operations in the same order as dynslam_amd/synth.py (render,
+    _ray_box, _shade, quantise), so the images are bit for bit StreetScene.frame's (tests/test_bench_contract.py); the disparity
+    noise is drawn on the host by the same numpy generators, in threads.  The host generator takes ~1.5 s per 1242x375 frame, so
+    with it a plain run's setup would grow with --steps; here a frame costs a few ms.  Every division keeps a device tensor as the
+    divisor and an elementwise dividend: torch turns `scalar / t` and `t / scalar` into multiplications by a reciprocal, which
+    round differently."""
+    import torch
+    from concurrent.futures import ThreadPoolExecutor
+    from dynslam_amd import synth
+    sc = synth.StreetScene(w, h)
+    f64 = dict(dtype=torch.float64, device=dev)
+    dcam = torch.from_numpy(sc._dcam).to(dev)[None]  # [1,H,W,3]
+    fb = sc.fx * synth.KITTI_BASELINE_M
+    shade_base = torch.tensor([[150, 200, 255], [180, 120, 90], [170, 140, 110], [200, 200, 190], [190, 180, 160], [200, 40, 40],
+                               [40, 160, 60], [50, 80, 200], [220, 200, 40], [110, 110, 115], [230, 120, 20], [20, 200, 200],
+                               [200, 60, 200], [240, 240, 240], [90, 60, 30], [60, 90, 30], [30, 60, 90]], **f64)
+    assert shade_base.shape[0] == 17 and sc.noise_px > 0
+    noise = lambda i: np.random.default_rng([sc.seed, int(i)]).normal(0.0, sc.noise_px, size=(h, w))  # noqa: E731 (quantise)
+    full = lambda shape, v: torch.full(shape, v, **f64)  # noqa: E731
+    out, poses = [], [sc.pose(i) for i in range(first, first + n)]
+    with ThreadPoolExecutor(max(1, min(threads, os.cpu_count() or 1))) as pool:
+        for b0 in range(0, n, batch):
+            idx = list(range(first + b0, first + min(n, b0 + batch)))
+            B = len(idx)
+            noise_b = pool.map(noise, idx)
+            T = np.stack([p.astype(np.float64) for p in poses[b0:b0 + B]])
+            R, o = torch.from_numpy(T[:, :3, :3]).to(dev), T[:, :3, 3]
+            # d = dcam @ R.T, summed left to right as numpy does
+            d = torch.stack([dcam[..., 0] * R[:, j, 0, None, None] + dcam[..., 1] * R[:, j, 1, None, None]
+                             + dcam[..., 2] * R[:, j, 2, None, None] for j in range(3)], dim=-1)  # [B,H,W,3]
+            shape = (B, h, w)
+            tg = torch.from_numpy(1.65 - o[:, 1]).to(dev)[:, None, None].expand(shape) / d[..., 1]
+            inf = full(shape, np.inf)
+            tg = torch.where((d[..., 1] > 1e-9) & (tg > 1e-6), tg, inf)
+            best_t, best_id = tg, torch.isfinite(tg).to(torch.int64) * 9
+            best_axis = torch.zeros(shape, dtype=torch.int64, device=dev)
+            inv = torch.ones_like(d) / d
+            boxes = [sc._static_boxes(oz) for oz in o[:, 2]]
+            for k in range(len(boxes[0])):  # the same number of boxes for every frame
+                lo_o = torch.from_numpy(np.stack([bx[k][0] - o[b] for b, bx in enumerate(boxes)])).to(dev)[:, None, None, :]
+                hi_o = torch.from_numpy(np.stack([bx[k][1] - o[b] for b, bx in enumerate(boxes)])).to(dev)[:, None, None, :]
+                pid = torch.tensor([bx[k][2] for bx in boxes], dtype=torch.int64, device=dev)[:, None, None]
+                t0, t1 = lo_o * inv, hi_o * inv
+                tmin, tmax = torch.minimum(t0, t1), torch.maximum(t0, t1)
+                tn, tf = tmin.amax(dim=-1), tmax.amin(dim=-1)
+                t = torch.where((tf >= tn) & (tn > 1e-6), tn, inf)
+                m = t < best_t
+                best_t = torch.where(m, t, best_t)
+                best_id = torch.where(m, pid, best_id)
+                best_axis = torch.where(m, tmin.argmax(dim=-1), best_axis)
+            p = torch.from_numpy(o).to(dev)[:, None, None, :] + d * torch.where(torch.isfinite(best_t), best_t, 0.0)[..., None]
+            col = shade_base[best_id.clamp(0, 16)]
+            chk = (torch.floor(p[..., 0] * 2.0) + torch.floor(p[..., 1] * 2.0) + torch.floor(p[..., 2] * 2.0)).to(torch.int64) & 1
+            stripe = torch.floor(p[..., 2] * 0.5).to(torch.int64) & 1
+            f = 0.75 + 0.25 * chk.to(torch.float64) - 0.1 * stripe.to(torch.float64) + 0.05 * best_axis.to(torch.float64)
+            rgb = torch.clamp(col * f[..., None], 0, 255)
+            # quantise
+            fbt = full(shape, fb)
+            disp = torch.where(torch.isfinite(best_t), fbt / best_t, 0.0)
+            disp = disp + torch.from_numpy(np.stack(list(noise_b))).to(dev)
+            disp = torch.round(disp * 16.0) / full(shape, 16.0)
+            zq = torch.where(disp > 0, fbt / disp, inf)
+            ok = torch.isfinite(best_t) & (zq >= synth.MIN_DEPTH_M) & (zq <= synth.MAX_DEPTH_M)
+            depth_mm = torch.where(ok, torch.round(zq * 1000.0), 0.0).to(torch.int16)
+            rgba = torch.empty((B, h, w, 4), dtype=torch.uint8, device=dev)
+            rgba[..., :3] = rgb.to(torch.uint8)
+            rgba[..., 3] = 255
+            out += [(rgba[b], depth_mm[b]) for b in range(B)]
+    return out, poses
+
+
+DUMP_BLOCKS = 1024  # voxel blocks in the volume sample of --dump-outputs (the whole volume is gigabytes)
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(eng, out_dir, seed=0):
+    """--dump-outputs: what the timed path hands its caller after the last timed step, as out_dir/<name>.npy (float32, float64
+    for the counters): Prepare's raycast (render_* = dump_render_state: the min/max depth tiles, the raycast result, the ICP
+    maps points / normals and the shaded image) and the volume Integrate left: the positions and voxels (sdf, depth weight,
+    colour, colour weight) of a seeded sample of DUMP_BLOCKS allocated blocks, drawn from the blocks sorted by position so
+    that two builds that computed the same volume dump the same blocks.  Render maps beyond the 64 MB budget would be cut
+    to a seeded sample of pixels (not at 1242x375: ~43 MB in all).  -> {name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    arrays = {"render_" + k: v.astype(np.float32) for k, v in eng.dump_render_state().items()}
+    ht = eng.dump_hash_table()
+    used = ht[ht["ptr"] >= 0]
+    used = used[np.lexsort((used["pos"][:, 2], used["pos"][:, 1], used["pos"][:, 0]))]
+    pick = np.sort(rng.choice(len(used), size=min(DUMP_BLOCKS, len(used)), replace=False))
+    from dynslam_amd.engine import BLOCK_SIZE3, VOXEL_DTYPE
+    vox = np.concatenate([eng.dump_voxel_blocks(int(used["ptr"][j]), 1) for j in pick] + [np.empty((0, BLOCK_SIZE3), VOXEL_DTYPE)])
+    arrays["volume_block_pos"] = used["pos"][pick].astype(np.float32)
+    for field in ("sdf", "w_depth", "clr", "w_color"):
+        arrays["volume_" + field] = vox[field].astype(np.float32)
+    st = eng.get_stats()
+    arrays["stats"] = np.array([st.num_allocated_voxel_blocks, st.last_free_block_id, st.last_free_excess_list_id,
+                                st.no_visible_blocks, st.sticky_status, st.frames_processed], np.float64)
+    big = [k for k in arrays if k.startswith("render_") and k != "render_minmax"]
+    budget = DUMP_BYTES - sum(v.nbytes for k, v in arrays.items() if k not in big)
+    n_pix = eng.W * eng.H
+    if sum(arrays[k].nbytes for k in big) > budget:
+        keep = np.sort(rng.choice(n_pix, size=int(n_pix * budget / sum(arrays[k].nbytes for k in big)), replace=False))
+        for k in big:
+            arrays[k] = arrays[k].reshape(n_pix, -1)[keep]
+    assert sum(v.nbytes for v in arrays.values()) <= DUMP_BYTES
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return {k: v.shape for k, v in arrays.items()}
 
 
 def pmc_traffic(args, kernel, visible_blocks_per_launch):
@@ -382,15 +497,16 @@ def backend_name(tb):
     return "hip" if tb is None else f"test-seam:{tb.__name__}"
 
 
-_PREGENERATED = {}  # n_instances -> frames, filled by the parent of spawn_ranks() before it forks
+_PREGENERATED = {}  # (n_instances, frame count) -> frames, filled by the parent of spawn_ranks() before it forks
 _JOB_STORE = None  # this rank's handle of the job's rendezvous store when spawn_ranks() started it (rank 0 hosts the store)
 
 
 def frames_for(args, n_inst):
     """The synthetic frames of a leg: generated once per job (the forked ranks inherit the parent's copy)."""
-    if n_inst not in _PREGENERATED:
-        _PREGENERATED[n_inst] = make_frames(args.width, args.height, args.warmup + args.steps, n_inst)
-    return _PREGENERATED[n_inst]
+    key = (n_inst, args.warmup + args.steps)
+    if key not in _PREGENERATED:
+        _PREGENERATED[key] = make_frames(args.width, args.height, args.warmup + args.steps, n_inst)
+    return _PREGENERATED[key]
 
 
 def _n_inst_of_leg(V, has_static):
@@ -954,12 +1070,23 @@ def parse_args(argv=None):
     ap.add_argument("--no-nested-legs", action="store_true", help="skip configs[2] / configs[3] on one GPU / the short configs[4] leg of the N = 1 line")
     ap.add_argument("--no-scaling-leg", action="store_true",
                     help="N = 1: do not append north_star's scaling workload (8 instance volumes on this GPU) to the line")
+    ap.add_argument("--full", action="store_true",
+                    help="one-volume runs: everything beyond the headline figure as well: the C++-host legs, the CPU baseline, the HIP "
+                         "events of the roofline and the copy bandwidth it is read against, the scaling leg and the nested configs[2] / "
+                         "configs[3] / configs[4] legs, each of those at most AUX_STEPS (45) timed steps (the --no-* options above switch single items off "
+                         "again).  Without it a run "
+                         "sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (the raycast maps of Prepare, a seeded sample "
+                         "of the volume, the engine's counters) as DIR/<name>.npy, float32 / float64, < 64 MB in all")
     return ap.parse_args(argv)
 
 
 def main(argv=None):
     args = parse_args(argv)
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.dump_outputs and multi_gpu_legs(args, max(args.gpus, world_env)):
+        sys.exit("bench.py: --dump-outputs writes the outputs of one-volume runs only (not --gpus N > 1 or a multi-volume leg)")
     if args.gpus > 1 and "RANK" not in os.environ:
         # the driver's `python bench.py --gpus N ...`: no launcher around us, so the ranks are ours to start
         sys.exit(spawn_ranks(args, multi_gpu_legs(args, args.gpus)))
@@ -975,29 +1102,39 @@ def run_rank(args):
     if legs:
         return main_volumes(args, legs)
 
+    if not args.full:
+        # a plain run measures the headline and nothing else: no C++-host legs, CPU baseline, HIP events / roofline, copy
+        # bandwidth, scaling or nested legs (all of that is --full); the frames of configs[1] are rendered on the device
+        args.no_through_shim = args.no_cpu_baseline = args.no_profile = args.no_scaling_leg = args.no_nested_legs = True
+    device_inputs = not (args.instances or args.host_views)
+    # --full's other legs (C++ host, scaling, nested configs[2-4]) generate their frames on the host, ~1.5 s each: they run at
+    # most AUX_STEPS timed steps (after at most AUX_WARMUP), so that a long headline run does not make them take hours
+    aux = argparse.Namespace(**vars(args))
+    aux.steps, aux.warmup = min(args.steps, AUX_STEPS), min(args.warmup, AUX_WARMUP)
+
     # The C++ host (SURVEY 8d "through-shim") first, as processes of their own, before this process has generated a frame or
     # opened the device (the state in which profiles/r04s_through_shim_via_tool.log was measured).
     shim = None
     if (int(os.environ.get("RANK", "0")) == 0 and world_env == 1 and not args.no_through_shim
             and not (args.decay or args.swap or args.instances or args.host_views)):
         try:
-            shim = through_shim(args, with_instances=args.preset == "5mm")
+            shim = through_shim(aux, with_instances=args.preset == "5mm")
         except Exception as ex:
             shim = {"frames_per_s": None, "note": f"failed: {ex}"}
 
     # synthetic frames: the worker pool forks, which must happen before HIP / RCCL start
-    frames = frames_for(args, args.instances)
+    frames = None if device_inputs else frames_for(args, args.instances)
     # the N = 1 line also carries north_star's scaling workload (8 instance volumes) on this one GPU: the N = 1 point of the curve
     # whose N > 1 points are `python bench.py --gpus N`
     scaling_leg = (int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_scaling_leg and args.preset == "5mm"
                    and not (args.decay or args.swap or args.instances or args.host_views))
-    frames8 = frames_for(args, SCALING_VOLUMES) if scaling_leg else None
+    frames8 = frames_for(aux, SCALING_VOLUMES) if scaling_leg else None
     # ... and BASELINE.json's other configurations as nested legs, each with a `status`, so that the driver's line — not only
     # profiles/ — observes them: configs[2] engine-only, configs[3] time-sliced on this one GPU, and a short
     # configs[4] leg (4 mm, voxel GC + host swapping, structural invariants checked)
     nested_legs = scaling_leg and not args.no_nested_legs
     if nested_legs:
-        frames_for(args, 4); frames_for(args, SCALING_VOLUMES - 1); loop_frames_for(args)
+        frames_for(aux, 4); frames_for(aux, SCALING_VOLUMES - 1); loop_frames_for(aux)
 
 
     import torch
@@ -1021,16 +1158,21 @@ def run_rank(args):
     W, H, K, Wm = args.width, args.height, args.steps, args.warmup
     n_frames = Wm + K
     # inputs resident in HBM before the timed region
-    rgb_dev = [torch.from_numpy(f[0]).to(dev) for f in frames]
-    dep_dev = [torch.from_numpy(f[1]).to(dev) for f in frames]
-    poses = [f[2] for f in frames]
+    if device_inputs:
+        dev_frames, poses = device_frames(W, H, 0, n_frames, dev)
+        rgb_dev, dep_dev = [f[0] for f in dev_frames], [f[1] for f in dev_frames]
+        frames = [(None, None, T, []) for T in poses]
+    else:
+        rgb_dev = [torch.from_numpy(f[0]).to(dev) for f in frames]
+        dep_dev = [torch.from_numpy(f[1]).to(dev) for f in frames]
+        poses = [f[2] for f in frames]
     torch.cuda.synchronize()
 
     # measured device-to-device copy bandwidth of this GPU with the library's float4 grid-stride copy (MI355X_MICROARCH.md: 6.29 TB/s
     # for that kernel) — the roofline's "measured" denominator: 4 GiB per direction, clocks warm, best launch of each of 5 rounds
     # (dsr_measure_copy_bandwidth_spread); max / median / min over the rounds are reported
     copy_gbs = None
-    if rank == 0:
+    if rank == 0 and args.full:
         import ctypes as C
         from dynslam_amd.engine import load_hip_api
         g3 = (C.c_double * 3)()
@@ -1094,6 +1236,8 @@ def run_rank(args):
     prof = eng.profile_get() if not args.no_profile else []
     eng.profile_enable(False)
     stats = eng.get_stats()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs)
 
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -1106,7 +1250,10 @@ def run_rank(args):
         cpu = None
         if not args.no_cpu_baseline and world == 1:  # the CPU baseline is an N = 1 item
             try:
-                cpu = cpu_baseline(frames, W, H, args.preset, args.cpu_budget_s)
+                # _cpu_run reads at most 12 frames: host copies of those when the frames were rendered on the device
+                sample = frames if not device_inputs else [(r.cpu().numpy(), d.cpu().numpy(), T, []) for r, d, T in
+                                                           zip(rgb_dev[:12], dep_dev[:12], poses[:12])]
+                cpu = cpu_baseline(sample, W, H, args.preset, args.cpu_budget_s)
             except Exception as ex:  # the baseline must never take the bench line down
                 cpu = {"value": None, "unit": "frames/s", "cores": 1, "kind": "port", "sample": f"failed: {ex}"}
         out = {
@@ -1135,7 +1282,7 @@ def run_rank(args):
             try:
                 calib = make_calib(*sc.intrinsics(), W, H)
                 kinds = volume_settings(args.preset)
-                a = argparse.Namespace(**vars(args))
+                a = argparse.Namespace(**vars(aux))
                 a.volumes, a.cpu_budget_s = SCALING_VOLUMES, args.cpu_budget_s / 2
                 line = run_volumes(a, frames8, lambda kind: EngineCore(default_settings(**kinds[kind], device=local_rank, sync_status=0), calib),
                                    dev, 1, 0, False, has_static=False)
@@ -1156,9 +1303,9 @@ def run_rank(args):
                 roofline["composite_frac"] = roofline["composite"]["frac"]
         if nested_legs:
             calib = make_calib(*sc.intrinsics(), W, H)
-            for key, fn in (("configs2", lambda: leg_configs2(args, dev, local_rank, calib)),
-                            ("configs3_1gpu", lambda: leg_configs3_1gpu(args, dev, local_rank, calib)),
-                            ("configs4_short", lambda: leg_configs4_short(args, dev, local_rank, calib))):
+            for key, fn in (("configs2", lambda: leg_configs2(aux, dev, local_rank, calib)),
+                            ("configs3_1gpu", lambda: leg_configs3_1gpu(aux, dev, local_rank, calib)),
+                            ("configs4_short", lambda: leg_configs4_short(aux, dev, local_rank, calib))):
                 try:
                     out[key] = dict(fn(), status="ok")
                 except Exception as ex:  # a nested leg must never take the line down; its status says what happened

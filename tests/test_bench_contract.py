@@ -302,3 +302,65 @@ def test_timed_regions_run_with_the_cyclic_collector_paused():
         assert not gc.isenabled()  # a caller that runs without the collector keeps running without it
     finally:
         gc.enable()
+
+
+# ---------------------------------------------------------------------------------------------------------
+# A plain `bench.py --gpus 1` renders its frames on the device (bench.device_frames): they must be StreetScene.frame's, bit for
+# bit, or the run would measure — and --dump-outputs report — another workload than the host generator's.
+
+def _frames_equal_synth(dev, w, h, first, n):
+    import torch
+    from dynslam_amd.synth import StreetScene
+    got, poses = bench.device_frames(w, h, first, n, torch.device(dev), batch=3)
+    sc = StreetScene(w, h)
+    assert len(got) == n
+    for k in range(n):
+        rgba, depth, T, _ = sc.frame(first + k)
+        assert np.array_equal(got[k][0].cpu().numpy(), rgba) and np.array_equal(got[k][1].cpu().numpy(), depth), first + k
+        assert np.array_equal(poses[k], T)
+
+
+def test_device_frames_equal_the_host_generator():
+    _frames_equal_synth("cpu", 160, 48, 0, 4)
+    _frames_equal_synth("cpu", 1242, 375, 997, 1)
+
+
+@pytest.mark.gpu
+def test_device_frames_equal_the_host_generator_on_the_gpu(hip_api):
+    _frames_equal_synth("cuda", 1242, 375, 0, 4)
+    _frames_equal_synth("cuda", 1242, 375, 2001, 2)
+
+
+def test_plain_run_options():
+    a = bench.parse_args(["--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_outputs_of_the_oracle_engine(tmp_path):
+    """--dump-outputs' writer on a small run of the CPU oracle: float32 / float64 .npy files, the same bytes for the same run."""
+    import torch
+    from dynslam_amd.engine import make_calib
+    from dynslam_amd.synth import StreetScene
+    from oracle.oracle import OracleEngine, oracle_settings
+    W, H = 160, 48
+    kw = dict(voxel_size=0.05, mu=0.2, max_w=100, view_frustum_min=0.2, view_frustum_max=30.0,
+              sdf_local_block_num=20000, hash_bucket_num=0x8000, excess_list_size=0x2000)
+    frames, poses = bench.device_frames(W, H, 0, 3, torch.device("cpu"))
+    dumps = []
+    for run in range(2):
+        e = OracleEngine(oracle_settings(**kw), make_calib(*StreetScene(W, H).intrinsics(), W, H))
+        for (rgba, depth), T in zip(frames, poses):
+            e.update_view(rgba.numpy(), depth.numpy())
+            e.set_pose_inv_m(T)
+            e.process_frame()
+            e.prepare()
+        shapes = bench.dump_outputs(e, str(tmp_path / str(run)))
+        e.close()
+        dumps.append({k: np.load(tmp_path / str(run) / (k + ".npy")) for k in shapes})
+    assert dumps[0].keys() == dumps[1].keys() and "render_points" in dumps[0] and "volume_sdf" in dumps[0]
+    assert all(v.dtype in (np.float32, np.float64) for v in dumps[0].values())
+    assert sum(v.nbytes for v in dumps[0].values()) <= 64 << 20
+    assert dumps[0]["render_points"].shape == (H, W, 4) and dumps[0]["stats"][0] > 0
+    assert all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])

@@ -8,8 +8,8 @@ CPU (here, where /root/reference exists):
     the forwarding headers under shim/InfiniTAM/ — the only other headers are the functional stand-ins for
     OpenCV / Eigen / Pangolin / gflags / libviso2 under tests/stubs/ (none is installed or vendored);
   * they LINK with shim/host_bench.cpp (-DDSR_HOST_REFERENCE_DRIVER) and libdsr_hip.so into
-    tests/refhost/_build/ref_driver_host: every ITMLib symbol the reference's driver needs resolves.
-GPU (the prebuilt binary travels with the snapshot; /root/reference does not exist there):
+    oracle/_ref/ref_driver_host: every ITMLib symbol the reference's driver needs resolves.
+GPU (the binary __graft_entry__.build() left in oracle/_ref/ travels with the tree; the reference's sources do not):
   * the reference's `dynslam::drivers::InfiniTamDriver` — UpdateView(cv::Mat3b, cv::Mat1s), SetPose(Eigen),
     Integrate, PrepareNextStep, Decay, GetImage / GetFloatImage(pangolin::OpenGlMatrix) — runs on the HIP
     engine and produces bit for bit what the Python mirror and our own C++ HostDriver produce.
@@ -20,12 +20,14 @@ import subprocess
 import numpy as np
 import pytest
 
+from oracle import ref_hosts
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference/src/DynSLAM"
 LIB_DIR = os.path.join(ROOT, "dynslam_amd", "csrc")
-REF_EXE = os.path.join(ROOT, "tests", "refhost", "_build", "ref_driver_host")
+REF_EXE = ref_hosts.DRIVER_HOST  # oracle/_ref/ref_driver_host
 SHIM_EXE = os.path.join(ROOT, "shim", "host_bench")
-LINK = ["-L", LIB_DIR, "-ldsr_hip", f"-Wl,-rpath,{LIB_DIR}", "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib"]
+LINK = ["-L", LIB_DIR, "-ldsr_hip", ref_hosts.rpath(LIB_DIR, SHIM_EXE), "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib"]
 REF_INC = ["-I", os.path.join(ROOT, "tests", "stubs"), "-I", os.path.join(ROOT, "tests", "stubs", "DynSLAM"),
            "-I", os.path.join(ROOT, "tests", "stubs", "DynSLAM", "InstRecLib"),
            "-I", os.path.join(ROOT, "shim", "DynSLAM"), "-I", os.path.join(ROOT, "shim", "DynSLAM", "InstRecLib"),
@@ -58,11 +60,7 @@ def build_shim_host():
 
 
 def build_ref_host():
-    os.makedirs(os.path.dirname(REF_EXE), exist_ok=True)
-    subprocess.check_call(["g++", "-std=c++14", "-O2", "-DNDEBUG", "-DDSR_HOST_REFERENCE_DRIVER"] + REF_INC +
-                          [os.path.join(ROOT, "shim", "host_bench.cpp"), os.path.join(REF, "InfiniTamDriver.cpp"),
-                           os.path.join(REF, "Utils.cpp"), "-o", REF_EXE] + LINK)
-    return REF_EXE
+    return ref_hosts.build_driver_host(force=True)
 
 
 @pytest.mark.skipif(not have_ref, reason="/root/reference is not on this machine")
@@ -357,10 +355,10 @@ def test_reference_driver_runs_on_the_hip_engine(hip_api, tmp_path):
     exes = [build_shim_host()]
     if have_ref:
         build_ref_host()
-    if os.path.exists(REF_EXE):  # prebuilt where /root/reference exists; shipped to the GPU box with the snapshot
+    if os.path.exists(REF_EXE):  # built by __graft_entry__.build() where the reference's sources exist; travels with oracle/_ref/
         exes.append(REF_EXE)
     else:
-        pytest.fail("tests/refhost/_build/ref_driver_host is missing: __graft_entry__.build() makes it where /root/reference exists")
+        pytest.fail("oracle/_ref/ref_driver_host is missing: __graft_entry__.build() makes it where the reference's sources exist")
     # the same call sequence through the Python mirror
     e = EngineCore(default_settings(**KW), make_calib(fx, fy, cx, cy, W, H))
     for i in range(n):
@@ -382,7 +380,7 @@ def test_reference_driver_runs_on_the_hip_engine(hip_api, tmp_path):
     h = fnv(bgr.tobytes(), fnv(mm.tobytes(), fnv(vdepth.tobytes(), fnv(dep.tobytes(), fnv(col.tobytes())))))
     assert (dep > 0).mean() > 0.05 and st.decayed_block_count > 0
     for exe in exes:
-        out = subprocess.check_output([exe] + args).decode().strip()
+        out = subprocess.check_output([exe] + args, env=ref_hosts.run_env()).decode().strip()
         got = dict(kv.split("=") for kv in out.split())
         assert int(got["used_bytes"]) == 8 * 512 * (st.num_allocated_voxel_blocks - st.last_free_block_id), out
         assert int(got["saved_bytes"]) == st.decayed_block_count * 4096, out

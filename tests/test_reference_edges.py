@@ -35,8 +35,8 @@ def ref():
         if torch.cuda.is_available():  # on a GPU box these are the only tests pinned by the reference's own code
             pytest.fail(msg)
         pytest.skip(msg)
-    from dynslam_amd import _capi
-    _capi.preload_hip_runtime()
+    from dynslam_amd.engine import load_hip_api
+    load_hip_api()  # libdsr_hip.so, RTLD_GLOBAL: the library's shim symbols resolve there (it does not name it, oracle/Makefile)
     return C.CDLL(REF_LIB)
 
 

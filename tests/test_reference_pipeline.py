@@ -22,16 +22,15 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests.refhost import build_pipeline as bp
+from oracle import ref_hosts as bp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "tests", "refhost", "_build")
 N_FRAMES = 8
 W, H = 1242, 375
 
 
 def run_host(exe, root, out_bin, decay=0, evaluate=0, extra_env=None):
-    env = dict(os.environ, OMP_NUM_THREADS=str(min(16, os.cpu_count() or 1)), **(extra_env or {}))
+    env = dict(bp.run_env(), OMP_NUM_THREADS=str(min(16, os.cpu_count() or 1)), **(extra_env or {}))
     r = subprocess.run([exe, root, str(N_FRAMES), out_bin, "0.05", str(decay), str(evaluate)], cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = r.stdout.strip().splitlines()[-1]
@@ -69,7 +68,7 @@ def dataset(tmp_path_factory):
 @pytest.fixture(scope="module")
 def oracle_host(tmp_path_factory):
     if not bp.have_reference():
-        pre = os.path.join(BUILD, "ref_dynslam_host_orc")
+        pre = bp.PIPELINE_HOST_ORC
         if os.path.exists(pre):
             return pre
         pytest.skip("/root/reference is not on this machine and no prebuilt host")
@@ -225,10 +224,10 @@ def test_reference_evaluation_scores_the_engine_renders_against_lidar(oracle_hos
 
 @pytest.mark.gpu
 def test_reference_pipeline_on_the_hip_engine_matches_the_oracle(tmp_path):
-    hip, orc = os.path.join(BUILD, "ref_dynslam_host"), os.path.join(BUILD, "ref_dynslam_host_orc")
+    hip, orc = bp.PIPELINE_HOST, bp.PIPELINE_HOST_ORC
     if not (os.path.exists(hip) and os.path.exists(orc)):
-        pytest.fail("tests/refhost/_build/ref_dynslam_host{,_orc} are missing: __graft_entry__.build() makes them where "
-                    "/root/reference exists and they travel to the GPU box with the snapshot")
+        pytest.fail("oracle/_ref/ref_dynslam_host{,_orc} are missing: __graft_entry__.build() makes them where "
+                    "the reference's sources exist and they travel to the GPU box with oracle/_ref/")
     from tests.refhost.make_dataset import write_dataset
     root = str(tmp_path / "kitti_like")
     os.makedirs(root)

@@ -59,7 +59,7 @@ def test_reference_pipeline_is_clean_under_asan_and_ubsan(sanitised, tmp_path):
     host keeps views, engines and tracks alive in its own order (a track's views outlive its engine, engines are created
     mid-sequence, reaped, destroyed) — the shim must stay memory-safe under exactly that usage.  The reference's own
     new[] / delete mismatches and leaks (VelodyneIO.h:52, Track pointers) are not ours to fix: those two checks are off."""
-    from tests.refhost import build_pipeline as bp
+    from oracle import ref_hosts as bp
     from tests.refhost.make_dataset import write_dataset
     if not bp.have_reference():
         pytest.skip("/root/reference is not on this machine")

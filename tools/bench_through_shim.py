@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Through-shim throughput: the C++ host shim/host_bench (our HostDriver over
-shim/ITMLib.h; with --reference the prebuilt tests/refhost/_build/ref_driver_host = the reference's
+shim/ITMLib.h; with --reference the prebuilt oracle/_ref/ref_driver_host = the reference's
 own InfiniTamDriver class) fed with pageable host frames of the bench workload, every frame paying
 what DynSLAM's host pays: BGR->RGBA, H2D of the frame, ProcessFrame, Prepare, the two preview
 conversions with their D2H copies, one status synchronisation.
@@ -52,7 +52,8 @@ def run(exe, frames, W, H, intr, preset_kw, warmup, decay=None, tmpdir=None, ins
         if instances:  # configs[2]: silhouettes split on the GPU, one volume per instance (shim/host_bench.cpp --masks)
             write_masks(path + ".masks", frames)
             args += ["--masks", path + ".masks", str(instances)]
-        out = subprocess.check_output(args, timeout=600).decode().strip()
+        from oracle.ref_hosts import run_env  # the libraries of this tree, wherever the executable lies
+        out = subprocess.check_output(args, timeout=600, env=run_env()).decode().strip()
     finally:
         os.unlink(path)
         if os.path.exists(path + ".masks"):
@@ -74,7 +75,7 @@ if __name__ == "__main__":
     from bench import PRESETS, make_frames
     from dynslam_amd.synth import StreetScene
     frames = make_frames(a.width, a.height, a.warmup + a.steps, a.instances)
-    exe = os.path.join(ROOT, "tests", "refhost", "_build", "ref_driver_host") if a.reference else os.path.join(ROOT, "shim", "host_bench")
+    exe = os.path.join(ROOT, "oracle", "_ref", "ref_driver_host") if a.reference else os.path.join(ROOT, "shim", "host_bench")
     r = run(exe, frames, a.width, a.height, StreetScene(a.width, a.height).intrinsics(), PRESETS[a.preset], a.warmup,
             (1, 200) if a.decay else None, instances=a.instances)
     print(r)

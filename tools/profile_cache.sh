@@ -7,7 +7,7 @@ export DSR_BENCH_NO_POOL=1
 TAG=${1:-r02}
 O=$GRAFT_REPO_ROOT/gpurun_out/cache_$TAG
 rm -rf $O; mkdir -p $O
-B="python bench.py --steps 10 --warmup 5 --no-cpu-baseline --no-through-shim --no-profile"
+B="python bench.py --full --steps 10 --warmup 5 --no-cpu-baseline --no-through-shim --no-profile"
 i=0
 for G in "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_EA0_RDREQ_sum" \
          "TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum TCP_PENDING_STALL_CYCLES_sum TCP_TCC_READ_REQ_LATENCY_sum" \

@@ -7,7 +7,7 @@ export DSR_BENCH_NO_POOL=1   # no forked worker pool under the profiler (it has 
 TAG=${1:-r02}
 O=$GRAFT_REPO_ROOT/gpurun_out/pmc_$TAG
 rm -rf $O; mkdir -p $O
-B="python bench.py --steps 10 --warmup 5 --no-cpu-baseline --no-through-shim --no-profile"
+B="python bench.py --full --steps 10 --warmup 5 --no-cpu-baseline --no-through-shim --no-profile"
 pass() {  # name, counters...
   local name=$1; shift
   for attempt in 1; do
@@ -23,7 +23,7 @@ pass inst SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_INS
 pass cyc SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_SCA SQ_INST_CYCLES_SALU
 python tools/profile_summary.py pmc $O/inst $O/cyc > $O/pmc_sq.json
 fi
-timeout 100 python bench.py --steps 10 --warmup 5 --no-cpu-baseline --no-through-shim > $O/bench_line.json 2> $O/bench.err
+timeout 100 python bench.py --full --steps 10 --warmup 5 --no-cpu-baseline --no-through-shim > $O/bench_line.json 2> $O/bench.err
 python tools/profile_summary.py traffic $O/fetch $O/write 10 $O/bench_line.json > $O/pmc_traffic.json
 find $O -name "*.csv" -delete
 rm -rf $O/fetch $O/write $O/inst $O/cyc

@@ -7,9 +7,9 @@ export DSR_BENCH_NO_POOL=1   # no forked worker pool under the profiler (it has 
 TAG=${1:-r02a}
 O=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG
 rm -rf $O; mkdir -p $O
-B="timeout 200 python bench.py --steps 45 --warmup 5 --no-cpu-baseline --no-through-shim --no-profile"
-timeout 300 python bench.py > $O/bench_line.json 2> $O/bench.err
-timeout 400 rocprofv3 --kernel-trace --stats -d $O/kt -o kt --output-format csv -- python bench.py --no-cpu-baseline --no-through-shim > $O/kt.log 2>&1
+B="timeout 200 python bench.py --full --steps 45 --warmup 5 --no-cpu-baseline --no-through-shim --no-profile"
+timeout 300 python bench.py --full > $O/bench_line.json 2> $O/bench.err
+timeout 400 rocprofv3 --kernel-trace --stats -d $O/kt -o kt --output-format csv -- python bench.py --full --no-cpu-baseline --no-through-shim > $O/kt.log 2>&1
 grep '^{"metric"' $O/kt.log > $O/bench_line_under_rocprof.json
 timeout 400 rocprofv3 --pmc FETCH_SIZE -d $O/fetch -o p --output-format csv -- $B > $O/fetch.log 2>&1
 timeout 400 rocprofv3 --pmc WRITE_SIZE -d $O/write -o p --output-format csv -- $B > $O/write.log 2>&1
