@@ -234,3 +234,52 @@ def bind(lib, prefix, allow_missing=False):
     ns.lib = lib
     ns.prefix = prefix
     return ns
+
+
+# ---- include/dsr_track.h: the ICP depth tracker.  A table of its own: dsr.h's SIGNATURES is what the CPU oracle mirrors
+# symbol for symbol, and the oracle has no tracker.
+TRACK_ABI_VERSION = 1  # == DSR_TRACK_ABI_VERSION
+TRACK_MAX_LEVELS = 8
+TRACK_ROTATION, TRACK_TRANSLATION, TRACK_BOTH, TRACK_NONE = 1, 2, 3, 4  # dsr_track_regime (upstream's TrackerIterationType)
+
+
+class TrackSettings(C.Structure):  # dsr_track_settings
+    _fields_ = [("no_hierarchy_levels", C.c_int32), ("tracking_regime", C.c_int32 * TRACK_MAX_LEVELS),
+                ("iterations", C.c_int32 * TRACK_MAX_LEVELS), ("no_icp_run_till_level", C.c_int32),
+                ("dist_threshold", C.c_float), ("termination_threshold", C.c_float)]
+
+
+class TrackResult(C.Structure):  # dsr_track_result
+    _fields_ = [("iterations", C.c_int32), ("valid_points", C.c_int32), ("f", C.c_float), ("had_point_cloud", C.c_int32),
+                ("m", C.c_float * 16), ("inv_m", C.c_float * 16)]
+
+
+class TrackLogEntry(C.Structure):  # dsr_track_log_entry
+    _fields_ = [("level", C.c_int32), ("iteration", C.c_int32), ("valid_points", C.c_int32), ("accepted", C.c_int32),
+                ("f", C.c_float), ("lambda_", C.c_float), ("step", C.c_float * 6), ("inv_m", C.c_float * 16)]
+
+
+assert C.sizeof(TrackSettings) == 80 and C.sizeof(TrackResult) == 144 and C.sizeof(TrackLogEntry) == 112
+
+TRACK_SIGNATURES = {
+    "track_abi_version": (C.c_int32, []),
+    "track_default_settings": (None, [C.POINTER(TrackSettings)]),
+    "track": (C.c_int, [_H, C.POINTER(TrackSettings), C.POINTER(TrackResult)]),
+    "track_get_log": (C.c_int, [_H, C.POINTER(TrackLogEntry), C.c_int32, C.POINTER(C.c_int32)]),
+    "track_get_pyramid": (C.c_int, [_H, _P, C.c_int64, C.POINTER(C.c_int64)]),
+}
+
+
+def bind_track(lib, prefix):
+    """The tracker's entry points `prefix + name` in `lib`, or None when the library has no tracker (the CPU oracle)."""
+    if not hasattr(lib, prefix + "track"):
+        return None
+    ns = SimpleNamespace()
+    for name, (res, args) in TRACK_SIGNATURES.items():
+        fn = getattr(lib, prefix + name)
+        fn.restype = res
+        fn.argtypes = args
+        setattr(ns, name, fn)
+    if ns.track_abi_version() != TRACK_ABI_VERSION:
+        raise ImportError("tracker ABI version mismatch (include/dsr_track.h)")
+    return ns

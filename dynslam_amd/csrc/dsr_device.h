@@ -105,7 +105,16 @@ struct SceneP {
   uint32_t *allocBits;    // entries that own a voxel block (ptr >= 0): set by the commit, cleared by the voxel GC
   int32_t *allocIds;      // the same set as an ASCENDING list of entry indices (ctr[CTR_NO_ALLOC_IDS] long, valid while
                           // ctr[CTR_ALLOC_IDS_VALID]): merged by the commit, rebuilt from allocBits after the GC (k_small.h, round 6)
+  // the point-cloud record (upstream's pose_pointCloud + age_pointCloud != -1): the world->camera pose the live ICP maps were
+  // rendered at, [16] = 1 once any kernel has written them.  Written by every kernel that writes the maps (write_icp_pose), read
+  // by the tracker (k_track.h); kept by a scene reset, like upstream's tracking state
+  float *icpPose;
 };
+constexpr int kIcpPoseWords = 20;
+// one workgroup of a kernel that is writing the live ICP maps for camera p.M leaves the record (plain vector stores)
+__device__ __forceinline__ void write_icp_pose(const SceneP &s, const Mat4 &M) {
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 17) s.icpPose[threadIdx.x] = threadIdx.x < 16 ? M.m[threadIdx.x] : 1.0f;
+}
 
 // ------------------------------------------------------------------ conversions
 

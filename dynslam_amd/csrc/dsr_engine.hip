@@ -10,6 +10,7 @@
 #include <sched.h>
 
 #include "dsr_internal.h"
+#include "dsr_math.h"
 using namespace dsr_internal;
 #include "k_alloc.h"
 #include "k_composite.h"
@@ -59,39 +60,8 @@ Mat4 m4_mul(const Mat4 &l, const Mat4 &r) {
   return o;
 }
 
-// ORUtils Matrix4::inv (cofactor expansion on the transposed source)
-bool m4_inv(const Mat4 &in, Mat4 &out) {
-  float t[12], s[16], det;
-  float *d = out.m;
-  for (int i = 0; i < 4; i++) { s[i] = in.m[i * 4]; s[i + 4] = in.m[i * 4 + 1]; s[i + 8] = in.m[i * 4 + 2]; s[i + 12] = in.m[i * 4 + 3]; }
-  t[0] = s[10] * s[15]; t[1] = s[11] * s[14]; t[2] = s[9] * s[15]; t[3] = s[11] * s[13];
-  t[4] = s[9] * s[14]; t[5] = s[10] * s[13]; t[6] = s[8] * s[15]; t[7] = s[11] * s[12];
-  t[8] = s[8] * s[14]; t[9] = s[10] * s[12]; t[10] = s[8] * s[13]; t[11] = s[9] * s[12];
-  d[0] = (t[0] * s[5] + t[3] * s[6] + t[4] * s[7]) - (t[1] * s[5] + t[2] * s[6] + t[5] * s[7]);
-  d[1] = (t[1] * s[4] + t[6] * s[6] + t[9] * s[7]) - (t[0] * s[4] + t[7] * s[6] + t[8] * s[7]);
-  d[2] = (t[2] * s[4] + t[7] * s[5] + t[10] * s[7]) - (t[3] * s[4] + t[6] * s[5] + t[11] * s[7]);
-  d[3] = (t[5] * s[4] + t[8] * s[5] + t[11] * s[6]) - (t[4] * s[4] + t[9] * s[5] + t[10] * s[6]);
-  d[4] = (t[1] * s[1] + t[2] * s[2] + t[5] * s[3]) - (t[0] * s[1] + t[3] * s[2] + t[4] * s[3]);
-  d[5] = (t[0] * s[0] + t[7] * s[2] + t[8] * s[3]) - (t[1] * s[0] + t[6] * s[2] + t[9] * s[3]);
-  d[6] = (t[3] * s[0] + t[6] * s[1] + t[11] * s[3]) - (t[2] * s[0] + t[7] * s[1] + t[10] * s[3]);
-  d[7] = (t[4] * s[0] + t[9] * s[1] + t[10] * s[2]) - (t[5] * s[0] + t[8] * s[1] + t[11] * s[2]);
-  t[0] = s[2] * s[7]; t[1] = s[3] * s[6]; t[2] = s[1] * s[7]; t[3] = s[3] * s[5];
-  t[4] = s[1] * s[6]; t[5] = s[2] * s[5]; t[6] = s[0] * s[7]; t[7] = s[3] * s[4];
-  t[8] = s[0] * s[6]; t[9] = s[2] * s[4]; t[10] = s[0] * s[5]; t[11] = s[1] * s[4];
-  d[8] = (t[0] * s[13] + t[3] * s[14] + t[4] * s[15]) - (t[1] * s[13] + t[2] * s[14] + t[5] * s[15]);
-  d[9] = (t[1] * s[12] + t[6] * s[14] + t[9] * s[15]) - (t[0] * s[12] + t[7] * s[14] + t[8] * s[15]);
-  d[10] = (t[2] * s[12] + t[7] * s[13] + t[10] * s[15]) - (t[3] * s[12] + t[6] * s[13] + t[11] * s[15]);
-  d[11] = (t[5] * s[12] + t[8] * s[13] + t[11] * s[14]) - (t[4] * s[12] + t[9] * s[13] + t[10] * s[14]);
-  d[12] = (t[2] * s[10] + t[5] * s[11] + t[1] * s[9]) - (t[4] * s[11] + t[0] * s[9] + t[3] * s[10]);
-  d[13] = (t[8] * s[11] + t[0] * s[8] + t[7] * s[10]) - (t[6] * s[10] + t[9] * s[11] + t[1] * s[8]);
-  d[14] = (t[6] * s[9] + t[11] * s[11] + t[3] * s[8]) - (t[10] * s[11] + t[2] * s[8] + t[7] * s[9]);
-  d[15] = (t[10] * s[10] + t[4] * s[8] + t[9] * s[9]) - (t[8] * s[9] + t[11] * s[10] + t[5] * s[8]);
-  det = s[0] * d[0] + s[1] * d[1] + s[2] * d[2] + s[3] * d[3];
-  if (det == 0.0f) return false;
-  float inv = 1.0f / det;
-  for (int i = 0; i < 16; i++) d[i] *= inv;
-  return true;
-}
+// ORUtils Matrix4::inv (cofactor expansion on the transposed source): dsr_math.h, shared with the tracker's device code
+bool m4_inv(const Mat4 &in, Mat4 &out) { return dsr_math::m4_inv(in.m, out.m); }
 
 }  // namespace
 
@@ -182,11 +152,12 @@ int reset_scene(dsr_engine *e) {
 void free_all(dsr_engine *e) {
   auto F = [](void *p) { if (p) (void)hipFree(p); };
   F(e->scene.table); F(e->scene.vba); F(e->scene.voxelAllocList); F(e->scene.excessAllocList);
-  F(e->scene.ctr); F(e->scene.work); F(e->scene.allocKey); F(e->scene.allocGrp); F(e->scene.allocTile);
+  F(e->scene.ctr); F(e->scene.icpPose); F(e->scene.work); F(e->scene.allocKey); F(e->scene.allocGrp); F(e->scene.allocTile);
   F(e->scene.visGrp); F(e->scene.visBits); F(e->scene.allocBits); F(e->scene.allocIds);
   for (RenderStateDev *rs : {&e->live, &e->freeview}) {
     F(rs->visibleIDs); F(rs->visibleIDsAlt); F(rs->visBlocks); F(rs->visBlocksAlt); F(rs->visType); F(rs->minmax); F(rs->raycastResult); F(rs->raycastImage); F(rs->rayBox);
   }
+  dsr_internal::tracker_free(e);
   F(e->tileSums); F(e->integrateStats); F(e->allocList); F(e->allocWork); F(e->meshTris); F(e->rgb); F(e->depth); F(e->depthTmp); F(e->rawDepth); F(e->pointsMap); F(e->normalsMap);
   F(e->freeDepth); F(e->aosScratch);
   F(e->fifoPlanes); F(e->decayCand); F(e->decayFlags);
@@ -672,6 +643,7 @@ int dsr_engine_create(const dsr_settings *settings, const dsr_calib *calib, dsr_
   ALLOC(dmalloc(&e->rawDepth, (size_t)e->P + 4));
   ALLOC(dmalloc(&e->pointsMap, (size_t)e->P));
   ALLOC(dmalloc(&e->normalsMap, (size_t)e->P));
+  ALLOC(dmalloc(&e->scene.icpPose, (size_t)kIcpPoseWords));
   ALLOC(dmalloc(&e->freeDepth, (size_t)e->P));
   ALLOC(dmalloc(&e->decayFlags, (size_t)e->noBlocks));
   ALLOC(dmalloc(&e->decayCand, (size_t)e->noBlocks));
@@ -718,6 +690,7 @@ int dsr_engine_create(const dsr_settings *settings, const dsr_calib *calib, dsr_
   }
   (void)hipMemsetAsync(e->pointsMap, 0, (size_t)e->P * 16, e->stream);
   (void)hipMemsetAsync(e->normalsMap, 0, (size_t)e->P * 16, e->stream);
+  (void)hipMemsetAsync(e->scene.icpPose, 0, kIcpPoseWords * sizeof(float), e->stream);  // no point cloud yet
   ALLOC(reset_scene(e));
   if (hipStreamSynchronize(e->stream) != hipSuccess) { free_all(e); delete e; return fail(DSR_E_DEVICE, "engine initialisation failed"); }
 #undef ALLOC

@@ -5,6 +5,7 @@
 //   dsr_exchange.hip  the multi-GPU layer exchange (RCCL, loaded on first use) and the compositing entry points
 //   dsr_hostio.hip    host-side I/O of the boundary: precomputed depth / disparity files, page-locking of the host's buffers
 //   dsr_profile.hip   HIP-event profile read-out, the division self-tests, the HBM copy probe
+//   dsr_track.hip     the ICP depth tracker (include/dsr_track.h): its buffers, the launch sequence of one dsr_track, the read-back
 // Every kernel header (k_*.h) is included by exactly ONE of them: kernels have external linkage.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -239,6 +240,8 @@ struct dsr_engine {
   bool rayBoxLive = false;   // the ray-box records have been initialised once (a later reset keeps their LAST / POSE part)
   struct { bool pending = false; FrameP p; } trackRender;
   struct dsr_batch *ownerBatch = nullptr;  // the volume batch this engine is a source / volume of (it may hold deferred work too)
+  // the ICP tracker's buffers (dsr_track.hip): allocated by the first dsr_track, so that engines that never track pay nothing
+  struct TrackerDev *tracker = nullptr;
 
   // profiling
   int profiling = 0;  // 0 off, 1 every kernel, 2 the two dominant kernels only
@@ -311,6 +314,8 @@ hipStream_t vstream(dsr_engine *e);
 // the pixels a cut-out into `instance`'s view has to write for a mask box (x0, y0, w, h), and the bookkeeping behind it
 void cutout_write_region(const dsr_engine *instance, bool direct, int x0, int y0, int w, int h, int wr[4]);
 void cutout_written(dsr_engine *instance, bool direct, int x0, int y0, int w, int h);
+// dsr_track.hip: the tracker's buffers of an engine being destroyed
+void tracker_free(dsr_engine *e);
 // dsr_engine.hip
 extern std::atomic<int> g_enginesOnDevice[64];  // live engines per device (range-image overlap policy, preview stores)
 int engine_set_device(dsr_engine *e);

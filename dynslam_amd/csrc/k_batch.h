@@ -147,7 +147,9 @@ __global__ __launch_bounds__(256) void k_batch_icp_maps(const BatchFrames frames
   const BatchFrameP &f = frames.f[blockIdx.z];
   if (!f.active) return;
   const BatchVolP &v = vols[blockIdx.z];
-  if (v.s.ctr[CTR_NO_VISIBLE_LIVE] <= 0 || (v.rayBox && !raybox_tile(v.rayBox, RB_DIRTY, blockIdx.x, blockIdx.y))) return;
+  if (v.s.ctr[CTR_NO_VISIBLE_LIVE] <= 0) return;
+  write_icp_pose(v.s, f.p.M);
+  if (v.rayBox && !raybox_tile(v.rayBox, RB_DIRTY, blockIdx.x, blockIdx.y)) return;
   const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
   if (x >= f.p.W || y >= f.p.H) return;
   float4 point, normal;

@@ -787,6 +787,7 @@ __global__ __launch_bounds__(256) void k_icp_maps(FrameP p, SceneP s, const floa
                                                   float4 *__restrict__ pointsMap, float4 *__restrict__ normalsMap,
                                                   uchar4 *__restrict__ outRendering) {
   if (s.ctr[CTR_NO_VISIBLE_LIVE] <= 0) return;
+  write_icp_pose(s, p.M);
   const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
   if (x >= p.W || y >= p.H) return;
   float4 point, normal;
@@ -801,7 +802,9 @@ __global__ __launch_bounds__(256) void k_icp_maps(FrameP p, SceneP s, const floa
 __global__ __launch_bounds__(256) void k_icp_maps_box(FrameP p, SceneP s, const float4 *__restrict__ pointsRay,
                                                       float4 *__restrict__ pointsMap, float4 *__restrict__ normalsMap,
                                                       uchar4 *__restrict__ outRendering, const int32_t *__restrict__ rb) {
-  if (s.ctr[CTR_NO_VISIBLE_LIVE] <= 0 || !raybox_tile(rb, RB_DIRTY, blockIdx.x, blockIdx.y)) return;
+  if (s.ctr[CTR_NO_VISIBLE_LIVE] <= 0) return;
+  write_icp_pose(s, p.M);  // (before the tile test: block (0, 0) need not be dirty)
+  if (!raybox_tile(rb, RB_DIRTY, blockIdx.x, blockIdx.y)) return;
   const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
   if (x >= p.W || y >= p.H) return;
   float4 point, normal;

@@ -430,6 +430,54 @@ class EngineCore:
         self._check(self.api.get_pose(self._h, _ptr(m), _ptr(im)))
         return _from_colmajor(m), _from_colmajor(im)
 
+    # -- tracking (include/dsr_track.h) ---------------------------------------
+    def _track_api(self):
+        if not hasattr(self, "_tapi"):
+            self._tapi = _capi.bind_track(self.api.lib, self.api.prefix)
+        if self._tapi is None:
+            raise DsrError(_capi.DSR_E_ARG, f"this backend ({self.api.prefix}*) has no ICP tracker: dsr_track is a libdsr_hip.so entry point")
+        return self._tapi
+
+    def track_default_settings(self):
+        s = _capi.TrackSettings()
+        self._track_api().track_default_settings(C.byref(s))
+        return s
+
+    def track(self, settings=None):
+        """ITMTrackingController::Track: ICP of the current view against the last Prepare's maps; the engine's pose becomes the
+        tracked one.  -> dict(iterations, valid_points, f, had_point_cloud, m, inv_m) with 4x4 row-major matrices."""
+        t = self._track_api()
+        if settings is None:
+            settings = self.track_default_settings()
+        r = _capi.TrackResult()
+        self._check(t.track(self._h, C.byref(settings), C.byref(r)))
+        return {"iterations": r.iterations, "valid_points": r.valid_points, "f": r.f, "had_point_cloud": bool(r.had_point_cloud),
+                "m": _from_colmajor(np.ctypeslib.as_array(r.m).copy()), "inv_m": _from_colmajor(np.ctypeslib.as_array(r.inv_m).copy())}
+
+    def track_log(self):
+        """The evaluations of the last track(): a structured array (level, iteration, valid_points, accepted, f, lambda_,
+        step[6], inv_m[16] column-major)."""
+        t = self._track_api()
+        n = C.c_int32(0)
+        self._check(t.track_get_log(self._h, None, 0, C.byref(n)))
+        buf = (_capi.TrackLogEntry * max(n.value, 1))()
+        self._check(t.track_get_log(self._h, buf, n.value, C.byref(n)))
+        return np.ctypeslib.as_array(buf)[:n.value].copy()
+
+    def track_pyramid(self):
+        """The depth pyramid of the last track(): [level 1, level 2, ...] as 2-D arrays."""
+        t = self._track_api()
+        n = C.c_int64(0)
+        self._check(t.track_get_pyramid(self._h, None, 0, C.byref(n)))
+        flat = np.empty(max(n.value, 1), np.float32)
+        self._check(t.track_get_pyramid(self._h, _ptr(flat), n.value, C.byref(n)))
+        out, off, w, h = [], 0, self.W, self.H
+        while off < n.value:
+            w, h = w // 2, h // 2
+            out.append(flat[off:off + w * h].reshape(h, w))
+            off += w * h
+        return out
+
     # -- fusion -------------------------------------------------------------
     def set_fusion_weight_params(self, depth_weighting):
         self._check(self.api.set_fusion_weight_params(self._h, int(bool(depth_weighting))))
@@ -596,6 +644,7 @@ class InfiniTamDriver:
     Same method names, argument meaning and error behaviour:
       UpdateView(rgb, raw_depth)  .cpp:211-224   (rgb here is RGBA uint8, depth int16 mm)
       SetPose(new_pose)           .h:131-135     (camera->world, sets pose_d.invM)
+      Track()                     .h:118-128     (ICP on the GPU, include/dsr_track.h; DsrError on the oracle)
       Integrate()                 .h:137-146     (raises OutOfBlocksError like the fork throws)
       PrepareNextStep()           .h:148-158
       Decay()/DecayCatchup()/Reap(w)  .h:201-235
@@ -632,6 +681,15 @@ class InfiniTamDriver:
 
     def GetLastEgomotion(self):
         return self._last_egomotion
+
+    def Track(self, settings=None):
+        """InfiniTamDriver::Track (InfiniTamDriver.h:118-128): ICP tracking of the current view against the last
+        PrepareNextStep; the egomotion is old_pose_inv * new_pose on GetInvM, as the reference stores it.  Raises DsrError on
+        a backend without a tracker (the CPU oracle)."""
+        _, old_inv = self.core.get_pose()
+        self.core.track(settings)
+        _, new_inv = self.core.get_pose()
+        self._last_egomotion = np.linalg.inv(old_inv) @ new_inv
 
     def Integrate(self):
         self.core.set_fusion_weight_params(self.use_depth_weighting)

@@ -24,6 +24,14 @@
 #include <vector>
 
 #include "../include/dsr.h"
+#include "../include/dsr_track.h"
+
+// The tracker's entry points are referenced WEAKLY: a host linked against a library without them (the CPU oracle's orc_* build
+// of the reference's hosts) still links, and ITMTrackingController::Track then throws as it did before the tracker existed.
+extern "C" {
+int dsr_track(dsr_engine *e, const dsr_track_settings *settings, dsr_track_result *out) __attribute__((weak));
+void dsr_track_default_settings(dsr_track_settings *out) __attribute__((weak));
+}
 
 #ifndef SDF_BLOCK_SIZE
 #define SDF_BLOCK_SIZE DSR_BLOCK_SIZE
@@ -219,6 +227,15 @@ struct ITMLibSettings {
   // (InstanceReconstructor.cpp:363-392: `new InfiniTamDriver(settings, ...)` per track) lands every track's volume on its own GPU
   int deviceIndex = -1;
   std::string groundTruthPoseFpath; int groundTruthPoseOffset = 0;
+  // upstream's depth-tracker settings (ITMLibSettings, as recalled: DESIGN.md Appendix D.1), read by ITMTrackingController::Track
+  enum TrackerIterationType { TRACKER_ITERATION_ROTATION = 1, TRACKER_ITERATION_TRANSLATION = 2, TRACKER_ITERATION_BOTH = 3,
+                              TRACKER_ITERATION_NONE = 4 };
+  int noHierarchyLevels = 5;
+  TrackerIterationType trackingRegime[DSR_TRACK_MAX_LEVELS] = {TRACKER_ITERATION_BOTH, TRACKER_ITERATION_BOTH, TRACKER_ITERATION_ROTATION,
+                                                               TRACKER_ITERATION_ROTATION, TRACKER_ITERATION_ROTATION};
+  int noICPRunTillLevel = 0;
+  float depthTrackerICPThreshold = 0.1f * 0.1f;
+  float depthTrackerTerminationThreshold = 1e-3f;
 };
 
 class ITMPose {
@@ -226,16 +243,18 @@ class ITMPose {
   ITMPose() { M.setIdentity(); invMSet.setIdentity(); }
   const Matrix4f &GetM() const { return M; }
   Matrix4f GetInvM() const { if (fromInv) return invMSet; Matrix4f r; M.inv(r); return r; }
-  void SetM(const Matrix4f &m) { M = m; fromInv = false; }
+  void SetM(const Matrix4f &m) { M = m; fromInv = false; exact = false; }
   // pose_d->SetInvM(...) is how the host sets poses (InfiniTamDriver.h:131-134): the matrix is
   // handed to the engine unchanged, which derives M with ORUtils' own inverse
-  void SetInvM(const Matrix4f &im) { invMSet = im; fromInv = true; im.inv(M); }
+  void SetInvM(const Matrix4f &im) { invMSet = im; fromInv = true; exact = false; im.inv(M); }
+  // the engine's pose after Track: M and its ORUtils inverse exactly as the engine holds them (dsr_track_result)
+  void SetFromEngine(const Matrix4f &m, const Matrix4f &im) { M = m; invMSet = im; fromInv = true; exact = true; }
   void SetFrom(const ITMPose *p) { *this = *p; }
   void Coerce() {}  // re-orthonormalisation: the engine takes M as given
-  int apply(dsr_engine *e) const { return fromInv ? dsr_set_pose_inv_m(e, invMSet.m) : dsr_set_pose_m(e, M.m); }
+  int apply(dsr_engine *e) const { return fromInv && !exact ? dsr_set_pose_inv_m(e, invMSet.m) : dsr_set_pose_m(e, M.m); }
  private:
   Matrix4f M, invMSet;
-  bool fromInv = false;
+  bool fromInv = false, exact = false;
 };
 
 struct ITMTrackingState { ITMPose *pose_d = new ITMPose; ~ITMTrackingState() { delete pose_d; } };
@@ -450,17 +469,37 @@ template <class TVoxel, class TIndex> class ITMDenseMapper {
   dsr_engine *e_;
 };
 
-// ITMTrackingController facade: Prepare only (InfiniTamDriver.h:152); Track() (ICP) is not on the path
+// ITMTrackingController facade: Prepare (InfiniTamDriver.h:152) and Track (InfiniTamDriver.h:118-128: ICP on the GPU, include/dsr_track.h)
 class ITMTrackingController {
  public:
-  explicit ITMTrackingController(dsr_engine *e) : e_(e) {}
+  explicit ITMTrackingController(dsr_engine *e, const ITMLibSettings *settings = nullptr) : e_(e), settings_(settings) {}
   void Prepare(ITMTrackingState *ts, const ITMView *, ITMRenderState *) {
     ITMLib::Engine::dsr_throw(ts->pose_d->apply(e_));
     ITMLib::Engine::dsr_throw(dsr_prepare(e_));
   }
-  void Track(ITMTrackingState *, const ITMView *) { throw std::runtime_error("ICP tracking is outside the dsr hot path (DynSLAM uses libviso2 poses)"); }
+  // the tracker runs on the engine's current view from the pose in `ts`; afterwards pose_d holds the engine's pose bit for bit
+  void Track(ITMTrackingState *ts, const ITMView *) {
+    if (!dsr_track || !dsr_track_default_settings) throw std::runtime_error("ICP tracking: this library has no tracker (dsr_track)");
+    ITMLib::Engine::dsr_throw(ts->pose_d->apply(e_));
+    dsr_track_settings s;
+    dsr_track_default_settings(&s);
+    if (settings_) {
+      s.no_hierarchy_levels = settings_->noHierarchyLevels;
+      for (int l = 0; l < DSR_TRACK_MAX_LEVELS; ++l) s.tracking_regime[l] = (int32_t)settings_->trackingRegime[l];
+      s.no_icp_run_till_level = settings_->noICPRunTillLevel;
+      s.dist_threshold = settings_->depthTrackerICPThreshold;
+      s.termination_threshold = settings_->depthTrackerTerminationThreshold;
+    }
+    dsr_track_result r;
+    ITMLib::Engine::dsr_throw(dsr_track(e_, &s, &r));
+    Matrix4f m, im;
+    std::memcpy(m.m, r.m, sizeof r.m);
+    std::memcpy(im.m, r.inv_m, sizeof r.inv_m);
+    ts->pose_d->SetFromEngine(m, im);
+  }
  private:
   dsr_engine *e_;
+  const ITMLibSettings *settings_;
 };
 
 // ITMViewBuilder facade (InfiniTamDriver.cpp:177,222-223)
@@ -522,7 +561,7 @@ class ITMMainEngine {
     ITMLib::Engine::dsr_throw(dsr_engine_create(&s, &c, &engine_));
     scene = new ITMScene<ITMVoxel, ITMVoxelIndex>(); scene->e = engine_; scene->sceneParams = &settings->sceneParams;
     denseMapper = new ITMDenseMapper<ITMVoxel, ITMVoxelIndex>(engine_);
-    trackingController = new ITMTrackingController(engine_);
+    trackingController = new ITMTrackingController(engine_, settings);
     viewBuilder = new ITMViewBuilder(engine_, calib);
     trackingState = new ITMTrackingState();
     renderState_live = new ITMRenderState_VH();

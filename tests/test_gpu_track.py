@@ -1,0 +1,337 @@
+"""ICP depth tracking on the GPU (include/dsr_track.h, k_track.h): the HIP tracker against its CPU restatement
+(tests/trackref/track_ref.cpp) bit for bit — depth pyramid, every evaluation of the log, the final pose — on map-sized and
+instance-sized volumes, through each form of the view pipeline and the short regimes; the point-cloud record; the reference's
+external_odo = false loop against the oracle + the CPU tracker; the shim's ITMTrackingController::Track and the Python mirror."""
+import os
+import shutil
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+from dynslam_amd import _capi
+from dynslam_amd.engine import DsrError, EngineCore, InfiniTamDriver, default_settings, make_calib
+from dynslam_amd.synth import StreetScene
+from tests import track_util as tu
+from tests.common import SMALL, assert_render_equal, assert_scene_equal
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+W, H = 320, 96
+
+
+def _settings(**kw):
+    return tu.default_settings(**kw)
+
+
+def _hip(sc, W_=W, H_=H, **kw):
+    s = dict(SMALL)
+    s.update(kw)
+    return EngineCore(default_settings(**s), make_calib(*sc.intrinsics(), W_, H_))
+
+
+def _fuse(e, sc, frames):
+    """fuse + prepare frames; -> M of the last Prepare (the maps' pose)"""
+    for i in frames:
+        rgba, d, T, _ = sc.frame(i)
+        e.update_view(rgba, d)
+        e.set_pose_inv_m(T)
+        e.process_frame()
+        e.prepare()
+    return e.get_pose()[0]
+
+
+def _check_against_ref(g, scene_m, settings, start):
+    """track g from `start` (inv_m) and compare everything with the restatement fed with g's own view and maps"""
+    g.set_pose_inv_m(start)
+    m0 = g.get_pose()
+    res = g.track(settings)
+    ref, ref_log, ref_pyr = tu.ref_track_engine(g, scene_m, settings, start=m0)
+    pyr = g.track_pyramid()
+    assert len(pyr) == len(ref_pyr)
+    for a, b in zip(pyr, ref_pyr):
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), "depth pyramid differs"
+    tu.assert_log_equal(g.track_log(), ref_log)
+    for k in ("iterations", "valid_points", "had_point_cloud"):
+        assert res[k] == ref[k], (k, res[k], ref[k])
+    assert np.float32(res["f"]).view(np.uint32) == np.float32(ref["f"]).view(np.uint32)
+    for k in ("m", "inv_m"):
+        assert np.array_equal(res[k].view(np.uint32), ref[k].view(np.uint32)), k
+    gm, gi = g.get_pose()
+    assert np.array_equal(gm, res["m"]) and np.array_equal(gi, res["inv_m"]), "the engine's pose is the tracked one"
+    return res, ref_log
+
+
+@pytest.mark.parametrize("vp,sync", [(_capi.VIEW_PIPELINE_AUTO, 0), (_capi.VIEW_PIPELINE_OFF, 1), (_capi.VIEW_PIPELINE_PER_ENGINE, 1),
+                                     (_capi.VIEW_PIPELINE_SHARED, 1)], ids=["auto", "off", "per_engine", "shared"])
+def test_map_volume_equals_cpu_restatement_on_oracle_maps(hip_api, vp, sync):
+    """map-sized volume at 320 x 96: the oracle's maps equal the HIP engine's (the existing suite's claim, checked here for this
+    state), the restatement is fed with the ORACLE's maps and view; upstream defaults (5 levels: levels 2-4 in the one-workgroup
+    kernel, 0-1 in the per-iteration pair) and 3 levels."""
+    from oracle.oracle import OracleEngine, oracle_settings
+    sc = StreetScene(W, H, noise_px=0.0)
+    calib = make_calib(*sc.intrinsics(), W, H)
+    g = EngineCore(default_settings(**SMALL, view_pipeline=vp, sync_status=sync), calib)
+    o = OracleEngine(oracle_settings(**SMALL), calib)
+    for e in (g, o):
+        scene_m = _fuse(e, sc, range(4))
+    assert_render_equal(g, o)
+    rgba, d, T, _ = sc.frame(4)
+    for e in (g, o):
+        e.update_view(rgba, d)
+    for levels in (5, 3):
+        settings = _settings(no_hierarchy_levels=levels)
+        start = tu.perturb(T)
+        g.set_pose_inv_m(start)
+        o.set_pose_inv_m(start)
+        m0 = o.get_pose()
+        res = g.track(settings)
+        ref, ref_log, ref_pyr = tu.ref_track_engine(o, scene_m, settings, start=m0)
+        for a, b in zip(g.track_pyramid(), ref_pyr):
+            assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+        tu.assert_log_equal(g.track_log(), ref_log)
+        assert np.array_equal(res["m"].view(np.uint32), ref["m"].view(np.uint32))
+        assert np.array_equal(res["inv_m"].view(np.uint32), ref["inv_m"].view(np.uint32))
+        assert res["iterations"] == ref["iterations"] > 0
+
+
+@pytest.mark.parametrize("regime", [[_capi.TRACK_ROTATION] * 5, [_capi.TRACK_TRANSLATION] * 5,
+                                    [_capi.TRACK_TRANSLATION, _capi.TRACK_ROTATION, _capi.TRACK_NONE, _capi.TRACK_BOTH, _capi.TRACK_TRANSLATION]],
+                         ids=["rotation", "translation", "mixed"])
+def test_short_regimes_equal_cpu_restatement(hip_api, regime):
+    sc = StreetScene(W, H, noise_px=0.0)
+    g = _hip(sc)
+    scene_m = _fuse(g, sc, range(4))
+    rgba, d, T, _ = sc.frame(4)
+    g.update_view(rgba, d)
+    res, log = _check_against_ref(g, scene_m, _settings(tracking_regime=regime), tu.perturb(T))
+    assert len(log) > 0
+    _check_against_ref(g, scene_m, _settings(tracking_regime=regime, no_icp_run_till_level=2), tu.perturb(T))
+
+
+def test_full_size_map_equals_cpu_restatement_on_its_own_maps(hip_api):
+    """1242 x 375 at 5 mm after 3 fused frames, upstream defaults: the restatement is fed with the HIP engine's own maps and view
+    (the existing suite proves those equal to the oracle's; the oracle at this size takes minutes).  Also: the same state tracked
+    twice gives the same bits."""
+    Wf, Hf = 1242, 375
+    kw = dict(voxel_size=0.005, mu=0.02, max_w=100, view_frustum_min=0.2, view_frustum_max=30.0,
+              sdf_local_block_num=1 << 21, hash_bucket_num=1 << 22, excess_list_size=1 << 20)
+    sc = StreetScene(Wf, Hf)
+    g = EngineCore(default_settings(**kw), make_calib(*sc.intrinsics(), Wf, Hf))
+    scene_m = _fuse(g, sc, range(3))
+    rgba, d, T, _ = sc.frame(3)
+    g.update_view(rgba, d)
+    start = tu.perturb(T)
+    res, log = _check_against_ref(g, scene_m, _settings(), start)
+    assert set(log["level"]) >= {0, 1, 2}
+    print(f"full size: {res['iterations']} evaluations, {res['valid_points']} points, error "
+          f"{tu.pose_error(start, T)} -> {tu.pose_error(res['inv_m'], T)} (m, deg)")
+    # determinism: the same state again
+    g.set_pose_inv_m(start)
+    again = g.track(_settings())
+    assert np.array_equal(again["m"], res["m"]) and np.array_equal(again["inv_m"], res["inv_m"])
+    tu.assert_log_equal(g.track_log(), log)
+
+
+@pytest.mark.parametrize("how", ["set_view_float", "split_silhouette"])
+def test_instance_volume_equals_cpu_restatement(hip_api, how):
+    """an instance-sized volume (k_small.h paths, deferred paired render) fed with a cut-out view: depth 0 outside the box"""
+    sc = StreetScene(W, H, noise_px=0.0)
+    calib = make_calib(*sc.intrinsics(), W, H)
+    inst = EngineCore(default_settings(**dict(SMALL, sdf_local_block_num=7142)), calib)
+    src = _hip(sc)
+    x0, y0, bw, bh = 40, 20, 200, 70
+    mask = np.ones((bh, bw), np.uint8)
+
+    def view(i):
+        rgba, d, T, _ = sc.frame(i)
+        if how == "set_view_float":
+            dm = np.zeros((H, W), np.float32)
+            dm[y0:y0 + bh, x0:x0 + bw] = d[y0:y0 + bh, x0:x0 + bw].astype(np.float32) * 0.001
+            inst.set_view_float(rgba, dm)
+        else:
+            src.update_view(rgba, d)
+            src.split_silhouette(inst, mask, x0, y0)
+        return T
+
+    for i in range(4):
+        T = view(i)
+        inst.set_pose_inv_m(T)
+        inst.process_frame()
+        inst.prepare()  # (deferred: queued by the next call)
+    scene_m = inst.get_pose()[0]
+    T = view(4)
+    res, log = _check_against_ref(inst, scene_m, _settings(no_hierarchy_levels=3), tu.perturb(T))
+    assert res["had_point_cloud"] and len(log) > 0
+
+
+def test_point_cloud_record(hip_api):
+    """Track before any Prepare: no-op.  After a frame with zero visible blocks (its Prepare writes no map), Track uses the
+    previous Prepare's pose and maps.  After dsr_reset_scene the point cloud is still used (the reference's ResetScene resets
+    the scene only, InfiniTamDriver.h:282-284)."""
+    sc = StreetScene(W, H, noise_px=0.0)
+    g = _hip(sc)
+    rgba, d, T, _ = sc.frame(0)
+    g.update_view(rgba, d)
+    g.set_pose_inv_m(T)
+    m0 = g.get_pose()
+    res = g.track(_settings())
+    assert not res["had_point_cloud"] and res["iterations"] == 0
+    assert np.array_equal(res["m"], m0[0]) and np.array_equal(res["inv_m"], m0[1])
+    scene_m = _fuse(g, sc, range(4))
+    # a frame that sees nothing: empty depth, camera far away
+    far = np.eye(4, dtype=np.float32)
+    far[:3, 3] = (5000.0, 0.0, 0.0)
+    g.update_view(rgba, np.zeros_like(d))
+    g.set_pose_inv_m(far)
+    g.process_frame()
+    g.prepare()
+    assert g.get_stats().no_visible_blocks == 0
+    rgba4, d4, T4, _ = sc.frame(4)
+    g.update_view(rgba4, d4)
+    res, _ = _check_against_ref(g, scene_m, _settings(no_hierarchy_levels=3), tu.perturb(T4))
+    assert res["had_point_cloud"]
+    g.reset_scene()
+    res, _ = _check_against_ref(g, scene_m, _settings(no_hierarchy_levels=3), tu.perturb(T4))
+    assert res["had_point_cloud"] and res["iterations"] > 0
+
+
+def test_closed_loop_equals_oracle_with_cpu_tracker(hip_api):
+    """The reference's external_odo = false order per frame (DynSlam.cpp:89-99 with the view updated first): UpdateView, Track,
+    Integrate, PrepareNextStep — on HIP with the GPU tracker, on the oracle with the CPU restatement's poses.  Poses and the
+    complete volume state are equal after every frame; the trajectory error against the synthetic ground truth is reported (each
+    frame starts 5.4 cm / 0.6 degrees off; the first maps hold one or two frames and are fused at the tracked poses, so upstream's
+    settings do not recover all of it: 5-10 cm, measured on the MI355X) and bounded only against divergence."""
+    from oracle.oracle import OracleEngine, oracle_settings
+    sc = StreetScene(W, H, noise_px=0.0)
+    calib = make_calib(*sc.intrinsics(), W, H)
+    g = EngineCore(default_settings(**SMALL), calib)
+    o = OracleEngine(oracle_settings(**SMALL), calib)
+    settings = _settings(no_hierarchy_levels=3)
+    errs = []
+    scene_m = None
+    for i in range(6):
+        rgba, d, T, _ = sc.frame(i)
+        start = T if i == 0 else tu.perturb(T)
+        for e in (g, o):
+            e.update_view(rgba, d)
+            e.set_pose_inv_m(start)
+        if i > 0:
+            g.track(settings)
+            ref, _, _ = tu.ref_track_engine(o, scene_m, settings)
+            o.set_pose_m(ref["m"])
+        gm, gi = g.get_pose()
+        om, oi = o.get_pose()
+        assert np.array_equal(gm, om) and np.array_equal(gi, oi), f"frame {i}: pose"
+        errs.append(tu.pose_error(gi, T))
+        for e in (g, o):
+            e.process_frame()
+            e.prepare()
+        scene_m = o.get_pose()[0]
+        assert_scene_equal(g, o)
+        assert_render_equal(g, o)
+    print("trajectory error per frame (m, deg):", [(round(a, 4), round(b, 3)) for a, b in errs])
+    assert max(a for a, _ in errs[1:]) < 0.3 and max(b for _, b in errs[1:]) < 3.0
+
+
+def test_driver_mirror_track_egomotion(hip_api):
+    """InfiniTamDriver.Track() (InfiniTamDriver.h:118-128): last egomotion = old_pose_inv * new_pose on GetInvM; the oracle has no
+    tracker and says so"""
+    from oracle.oracle import oracle_driver, oracle_settings
+    sc = StreetScene(W, H, noise_px=0.0)
+    calib = make_calib(*sc.intrinsics(), W, H)
+    drv = InfiniTamDriver(default_settings(**SMALL), calib)
+    for i in range(4):
+        rgba, d, T, _ = sc.frame(i)
+        drv.UpdateView(rgba, d)
+        drv.SetPose(T)
+        drv.Integrate()
+        drv.PrepareNextStep()
+    rgba, d, T, _ = sc.frame(4)
+    drv.UpdateView(rgba, d)
+    drv.SetPose(tu.perturb(T))
+    old = drv.GetPose()
+    drv.Track()
+    new = drv.GetPose()
+    assert not np.array_equal(old, new)
+    assert np.array_equal(drv.GetLastEgomotion(), np.linalg.inv(old) @ new)
+    od = oracle_driver(oracle_settings(**SMALL), calib)
+    od.UpdateView(rgba, d)
+    with pytest.raises(DsrError, match="no ICP tracker"):
+        od.Track()
+
+
+def test_refusals(hip_api, monkeypatch):
+    from dynslam_amd.engine import Batch
+    sc = StreetScene(W, H, noise_px=0.0)
+    g = _hip(sc)
+    rgba, d, T, _ = sc.frame(0)
+    g.update_view(rgba, d)
+    for bad in (dict(no_hierarchy_levels=9), dict(no_hierarchy_levels=0), dict(iterations=[2, -1, 6, 8, 10]),
+                dict(no_icp_run_till_level=5), dict(tracking_regime=[3, 3, 7, 1, 1]), dict(dist_threshold=float("nan"))):
+        with pytest.raises(DsrError) as ex:
+            g.track(_settings(**bad))
+        assert ex.value.status == _capi.DSR_E_ARG, bad
+    monkeypatch.setenv("DSR_PIPELINED_VIEW", "0")
+    calib = make_calib(*sc.intrinsics(), W, H)
+    src = EngineCore(default_settings(**SMALL), calib)
+    vol = EngineCore(default_settings(**dict(SMALL, sdf_local_block_num=7142)), calib)
+    batch = Batch(src, [vol])
+    vol.set_view_float(rgba, d.astype(np.float32) * 0.001)
+    with pytest.raises(DsrError) as ex:
+        vol.track()
+    assert ex.value.status == _capi.DSR_E_ARG and "batch" in str(ex.value)
+    batch.close()
+    vol.track()  # once the batch is gone the volume tracks again
+
+
+def _track_host():
+    exe = os.path.join(HERE, "trackhost", "_build", "track_host")
+    src = os.path.join(HERE, "trackhost", "track_host.cpp")
+    lib = os.path.join(ROOT, "dynslam_amd", "csrc", "libdsr_hip.so")
+    deps = [src, os.path.join(ROOT, "shim", "ITMLib.h"), os.path.join(ROOT, "include", "dsr_track.h"), lib]
+    if not os.path.exists(exe) or any(os.path.getmtime(p) > os.path.getmtime(exe) for p in deps):
+        if not shutil.which("g++"):
+            pytest.skip("g++ not available")
+        os.makedirs(os.path.dirname(exe), exist_ok=True)
+        tmp = exe + f".{os.getpid()}.tmp"
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I", os.path.join(ROOT, "shim"), src, "-o", tmp,
+                               "-L", os.path.dirname(lib), "-ldsr_hip", "-Wl,-rpath," + os.path.dirname(lib),
+                               "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib"])
+        os.replace(tmp, exe)
+    return exe
+
+
+def test_shim_tracking_controller_track(hip_api, tmp_path):
+    """tests/trackhost/track_host drives ITMTrackingController::Track through shim/ITMLib.h (it threw before the tracker
+    existed); pose_d afterwards equals dsr_track's result bit for bit, GetInvM included"""
+    exe = _track_host()
+    sc = StreetScene(W, H, noise_px=0.0)
+    n = 5
+    rgba, d, T, _ = sc.frame(n - 1)
+    start = tu.perturb(T)
+    inp = tmp_path / "in.bin"
+    with open(inp, "wb") as f:
+        f.write(struct.pack("<3i4f", W, H, n, *sc.intrinsics()))
+        for i in range(n):
+            rgba, d, Ti, _ = sc.frame(i)
+            f.write(np.ascontiguousarray(rgba, np.uint8).tobytes())
+            f.write(np.ascontiguousarray(d, np.int16).tobytes())
+            f.write(tu.colmajor(Ti).tobytes())
+        f.write(tu.colmajor(start).tobytes())
+    out = subprocess.run([exe, str(inp)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr
+    words = np.array([int(w, 16) for w in out.stdout.split()], np.uint32)
+    host_m, host_inv = words[:16].view(np.float32).reshape(4, 4).T, words[16:].view(np.float32).reshape(4, 4).T
+    g = EngineCore(default_settings(**SMALL, sync_status=1), make_calib(*sc.intrinsics(), W, H))
+    _fuse(g, sc, range(n - 1))
+    rgba, d, T, _ = sc.frame(n - 1)
+    g.update_view(rgba, d)
+    g.set_pose_inv_m(start)
+    res = g.track(_settings(no_hierarchy_levels=3))
+    assert res["iterations"] > 0
+    assert np.array_equal(host_m.view(np.uint32), res["m"].view(np.uint32))
+    assert np.array_equal(host_inv.view(np.uint32), res["inv_m"].view(np.uint32))
