@@ -238,7 +238,7 @@ def bind(lib, prefix, allow_missing=False):
 
 # ---- include/dsr_track.h: the ICP depth tracker.  A table of its own: dsr.h's SIGNATURES is what the CPU oracle mirrors
 # symbol for symbol, and the oracle has no tracker.
-TRACK_ABI_VERSION = 1  # == DSR_TRACK_ABI_VERSION
+TRACK_ABI_VERSION = 2  # == DSR_TRACK_ABI_VERSION (2: dsr_batch_fuse_tracked)
 TRACK_MAX_LEVELS = 8
 TRACK_ROTATION, TRACK_TRANSLATION, TRACK_BOTH, TRACK_NONE = 1, 2, 3, 4  # dsr_track_regime (upstream's TrackerIterationType)
 
@@ -267,6 +267,8 @@ TRACK_SIGNATURES = {
     "track": (C.c_int, [_H, C.POINTER(TrackSettings), C.POINTER(TrackResult)]),
     "track_get_log": (C.c_int, [_H, C.POINTER(TrackLogEntry), C.c_int32, C.POINTER(C.c_int32)]),
     "track_get_pyramid": (C.c_int, [_H, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "batch_fuse_tracked": (C.c_int, [_P, C.POINTER(BatchItem), C.c_int, C.POINTER(TrackSettings), C.POINTER(TrackResult),
+                                     C.POINTER(C.c_int32)]),
 }
 
 

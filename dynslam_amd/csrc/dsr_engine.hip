@@ -21,6 +21,7 @@ using namespace dsr_internal;
 #include "k_mesh.h"
 #include "k_small.h"
 #include "k_batch.h"
+#include "../../include/dsr_track.h"
 
 // the volume batch's deferred work (paired render; defined with dsr_batch below, inside its extern "C" block)
 extern "C" {
@@ -1180,6 +1181,7 @@ struct dsr_batch {
   bool pair = false, pendingTrack = false;
   BatchFrames liveFrames;
   BatchFrameP *freeTableDev = nullptr;
+  BatchTrackerDev *tracker = nullptr;  // the batch tracker's tables (dsr_track.hip), created by the first dsr_batch_fuse_tracked
 };
 namespace {
 std::mutex g_batchMutex;
@@ -1284,13 +1286,19 @@ void dsr_batch_destroy(dsr_batch *b) {
   }
   (void)hipFree(b->volsDev);
   (void)hipFree(b->freeTableDev);
+  batch_tracker_free(b->tracker);
   delete b;
 }
 
 // InstanceReconstructor::ProcessFrame for the instances of this GPU (InstanceReconstructor.cpp:238-263,569-700): per item, in the
 // host's order, ProcessSilhouette + RemoveSilhouette, SetPose, Integrate, PrepareNextStep — as 2 + 6 launches for ALL of them.
-int dsr_batch_fuse(dsr_batch *b, const dsr_batch_item *items, int n_items, int32_t *status_out) {
+// settings (dsr_batch_fuse_tracked; null: dsr_batch_fuse): Track between SetPose and Integrate, every volume in the same launches
+// (k_batch_track.h) and one host wait for all their poses; results (n_items, may be null): per item its dsr_track result.
+// Stages: checks, view split, [tracker], per-volume frame table, fusion launches.
+static int batch_fuse(dsr_batch *b, const dsr_batch_item *items, int n_items, const dsr_track_settings *settings,
+                      dsr_track_result *results, int32_t *status_out) {
   if (!b || !items || n_items <= 0) return fail(DSR_E_ARG, "bad batch arguments");
+  if (settings && batch_track_check(settings)) return DSR_E_ARG;  // (nothing queued yet: CHECK_E below may flush deferred work)
   dsr_engine *src = b->source;
   CHECK_E(src);
   if (!src->hasView) return fail(DSR_E_NO_VIEW, "no view yet");
@@ -1312,8 +1320,11 @@ int dsr_batch_fuse(dsr_batch *b, const dsr_batch_item *items, int n_items, int32
       if (!m4_inv(invM, M)) return fail(DSR_E_ARG, "singular pose");
     }
   }
-  int st = batch_refresh(b);
-  if (st) return st;
+  int st = DSR_OK;
+  if (settings)  // the tracker reads every volume's maps as its last Prepare left them: a tracking render a volume deferred before
+    for (dsr_engine *e : b->vols)  // the batch existed is queued too (the batch's own was, by CHECK_E above)
+      if (e->trackRender.pending && (st = engine_flush_deferred(e))) return st;
+  if ((st = batch_refresh(b))) return st;
   hipStream_t S = src->stream;
   // ---- the view split: every cut-out and every blanking in ceil(n / 8) passes over the frame
   if (anyBlank && (st = begin_view_modify(src))) return st;
@@ -1341,6 +1352,21 @@ int dsr_batch_fuse(dsr_batch *b, const dsr_batch_item *items, int n_items, int32
   }
   HIP_TRY(hipGetLastError());
   if (anyBlank && (st = view_written(src, S))) return st;
+  // ---- the tracker: SetPose(item.inv_m), Track of every volume with an item (InstanceReconstructor.cpp:624-650), one host wait
+  if (settings) {
+    if (results) memset(results, 0, sizeof(dsr_track_result) * (size_t)n_items);
+    dsr_engine *tv[kBatchMax];
+    int tvItem[kBatchMax];
+    int nt = 0;
+    for (int v = 0; v < nv; ++v) {
+      if (itemOf[v] < 0) continue;
+      if ((st = dsr_set_pose_inv_m(b->vols[v], items[itemOf[v]].inv_m))) return st;
+      tv[nt] = b->vols[v]; tvItem[nt] = itemOf[v]; nt++;
+    }
+    dsr_track_result res[kBatchMax];
+    if ((st = batch_track(src, tv, nt, settings, &b->tracker, res))) return st;
+    if (results) for (int k = 0; k < nt; ++k) results[tvItem[k]] = res[k];
+  }
   // ---- per volume: pose, this frame's parameters, the bookkeeping of allocate_scene / integrate_scene / dsr_prepare
   BatchFrames frames;
   memset(&frames, 0, sizeof frames);
@@ -1353,7 +1379,7 @@ int dsr_batch_fuse(dsr_batch *b, const dsr_batch_item *items, int n_items, int32
     if ((st = view_written(e, S))) return st;
     e->viewBox[0] = std::max(0, it.x0); e->viewBox[1] = std::max(0, it.y0);
     e->viewBox[2] = std::min(e->W, it.x0 + it.box_w); e->viewBox[3] = std::min(e->H, it.y0 + it.box_h);
-    if ((st = dsr_set_pose_inv_m(e, it.inv_m))) return st;
+    if (!settings && (st = dsr_set_pose_inv_m(e, it.inv_m))) return st;  // (tracked: the tracker's pose, exactly as it left it)
     float proj[4]; depth_proj(e, proj);
     BatchFrameP &f = fr[v];
     f.p = make_frame_params(e, e->M_d, e->invM_d, proj);
@@ -1413,6 +1439,15 @@ int dsr_batch_fuse(dsr_batch *b, const dsr_batch_item *items, int n_items, int32
     }
   }
   return DSR_OK;
+}
+
+int dsr_batch_fuse(dsr_batch *b, const dsr_batch_item *items, int n_items, int32_t *status_out) {
+  return batch_fuse(b, items, n_items, nullptr, nullptr, status_out);
+}
+int dsr_batch_fuse_tracked(dsr_batch *b, const dsr_batch_item *items, int n_items, const dsr_track_settings *settings,
+                           dsr_track_result *results, int32_t *status_out) {
+  if (!settings) return fail(DSR_E_ARG, "dsr_batch_fuse_tracked: null settings");
+  return batch_fuse(b, items, n_items, settings, results, status_out);
 }
 
 // GetImage + GetFloatImage of every listed volume from its own free camera (CompositeInstances, InstanceReconstructor.cpp:956-986):

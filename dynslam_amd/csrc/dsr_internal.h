@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "dsr_device.h"
+#include "../../include/dsr_track.h"
 
 using namespace dsr;
 
@@ -316,6 +317,14 @@ void cutout_write_region(const dsr_engine *instance, bool direct, int x0, int y0
 void cutout_written(dsr_engine *instance, bool direct, int x0, int y0, int w, int h);
 // dsr_track.hip: the tracker's buffers of an engine being destroyed
 void tracker_free(dsr_engine *e);
+// dsr_track.hip: the batch tracker (dsr_batch_fuse_tracked; k_batch_track.h).  batch_track_check: the settings, before anything
+// is queued.  batch_track: every engine of `vols` from its current pose (M_d / invM_d) on src's stream, ONE host wait, then each
+// engine's pose is the tracked one and out[k] (may be null) its result; *bt: the batch's tables, created on first use.
+struct BatchTrackerDev;
+int batch_track_check(const dsr_track_settings *settings);
+int batch_track(dsr_engine *src, dsr_engine *const *vols, int n, const dsr_track_settings *settings, BatchTrackerDev **bt,
+                dsr_track_result *out);
+void batch_tracker_free(BatchTrackerDev *bt);
 // dsr_engine.hip
 extern std::atomic<int> g_enginesOnDevice[64];  // live engines per device (range-image overlap policy, preview stores)
 int engine_set_device(dsr_engine *e);

@@ -1,9 +1,10 @@
-// dsr_track.hip — the ICP depth tracker's host side (include/dsr_track.h; kernels: k_track.h).
-// One dsr_track = at most 2 + 2 x (fine iterations) launches on the engine's stream and ONE host wait, for the final pose.
+// dsr_track.hip — the ICP depth tracker's host side (include/dsr_track.h; kernels: k_track.h, k_batch_track.h).
+// One dsr_track = at most 2 + 2 x (fine iterations) launches on the engine's stream and ONE host wait, for the final pose; the
+// batch tracker (dsr_batch_fuse_tracked) the same launches for all volumes of a batch and ONE host wait for all their poses.
 #include "dsr_internal.h"
 #include "../../include/dsr_track.h"
 #include "dsr_math.h"
-#include "k_track.h"
+#include "k_batch_track.h"
 
 extern "C" bool dsri_batch_is_live(dsr_batch *b);  // dsr_engine.hip
 using dsr_internal::after_fusion;
@@ -41,6 +42,22 @@ void tracker_free(dsr_engine *e) {
   delete t;
   e->tracker = nullptr;
 }
+
+struct BatchTrackerDev {
+  BatchTrackVol *tabDev = nullptr, *tabHost = nullptr;      // the volumes' records; host side pinned (uploaded in stream order)
+  TrackState *statesDev = nullptr, *statesHost = nullptr;  // every volume's state block; ONE read-back per call
+  hipEvent_t done = nullptr;
+  bool inFlight = false;  // a call queued the upload but did not reach its wait (an error return): wait before reusing tabHost
+};
+void batch_tracker_free(BatchTrackerDev *bt) {
+  if (!bt) return;
+  if (bt->tabDev) (void)hipFree(bt->tabDev);
+  if (bt->tabHost) (void)hipHostFree(bt->tabHost);
+  if (bt->statesDev) (void)hipFree(bt->statesDev);
+  if (bt->statesHost) (void)hipHostFree(bt->statesHost);
+  if (bt->done) (void)hipEventDestroy(bt->done);
+  delete bt;
+}
 }  // namespace dsr_internal
 
 namespace {
@@ -69,45 +86,14 @@ int check_settings(const dsr_track_settings *s) {
   return DSR_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int32_t dsr_track_abi_version(void) { return DSR_TRACK_ABI_VERSION; }
-
-void dsr_track_default_settings(dsr_track_settings *out) {
-  if (!out) return;
-  memset(out, 0, sizeof *out);
-  out->no_hierarchy_levels = 5;
-  const int regime[5] = {DSR_TRACK_BOTH, DSR_TRACK_BOTH, DSR_TRACK_ROTATION, DSR_TRACK_ROTATION, DSR_TRACK_ROTATION};
-  for (int l = 0; l < DSR_TRACK_MAX_LEVELS; ++l) {
-    out->tracking_regime[l] = l < 5 ? regime[l] : DSR_TRACK_NONE;
-    out->iterations[l] = 2 + 2 * l;  // upstream: 2 at level 0, + 2 per level
-  }
-  out->no_icp_run_till_level = 0;
-  out->dist_threshold = 0.1f * 0.1f;
-  out->termination_threshold = 1e-3f;
-}
-
-int dsr_track(dsr_engine *e, const dsr_track_settings *settings, dsr_track_result *out) {
-  if (!e || !settings) return fail(DSR_E_ARG, "null");
-  if (e->ownerBatch && dsri_batch_is_live(e->ownerBatch))
-    return fail(DSR_E_ARG, "dsr_track: the volume belongs to a live dsr_batch (tracking inside the batch is not supported)");
-  { int st = check_settings(settings); if (st) return st; }
-  CHECK_E(e);  // queues a deferred tracking render (paired render) first: the maps are the last Prepare's
-  if (!e->hasView) return fail(DSR_E_NO_VIEW, "no view yet");
+// the tracker's per-engine part of a call: the level table (sizes by integer halving, intrinsics x 0.5, distance thresholds
+// linear from thr / L (finest) to thr (coarsest)), the buffers (grown on demand), and which of the running levels go to the
+// one-workgroup kernel (*coarseLo; L: none).  Shared by dsr_track and the batch tracker, which launch the same bodies on it.
+int tracker_setup(dsr_engine *e, const dsr_track_settings *settings, TrackP &tp, int *coarseLo, size_t *pyrTotalOut) {
   if (!e->tracker) e->tracker = new (std::nothrow) TrackerDev();
   TrackerDev *t = e->tracker;
   if (!t) return fail(DSR_E_NOMEM, "tracker state");
-  if (!t->state) {
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&t->state), sizeof(TrackState)));
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&t->stateHost), sizeof(TrackState), hipHostMallocDefault));
-    HIP_TRY(hipEventCreateWithFlags(&t->done, hipEventDisableTiming));
-  }
-
-  // the levels: sizes by integer halving, intrinsics x 0.5, distance thresholds linear from thr / L (finest) to thr (coarsest)
   const int L = settings->no_hierarchy_levels;
-  TrackP tp;
   memset(&tp, 0, sizeof tp);
   tp.levels = L;
   float thr[DSR_TRACK_MAX_LEVELS];
@@ -134,10 +120,10 @@ int dsr_track(dsr_engine *e, const dsr_track_settings *settings, dsr_track_resul
   // which of the running levels go to the one-workgroup kernel: the levels >= 2 of at most kTrackCoarseMaxChunks chunks, from
   // the coarsest down to the first that is not
   const int lo = settings->no_icp_run_till_level;
-  int coarseLo = L;
+  *coarseLo = L;
   for (int l = L - 1; l >= std::max(lo, 2); --l) {
     if (tp.lv[l].chunks > kTrackCoarseMaxChunks) break;
-    coarseLo = l;
+    *coarseLo = l;
   }
   { int st = grow(&t->pyramid, t->pyramidCap, std::max(pyrTotal, (size_t)1)); if (st) return st; }
   { int st = grow(&t->part, t->partCap, maxChunks * kTrackVals); if (st) return st; }
@@ -153,6 +139,131 @@ int dsr_track(dsr_engine *e, const dsr_track_settings *settings, dsr_track_resul
   tp.sceneW = e->W; tp.sceneH = e->H;
   tp.sceneIntr = make_float4(e->calib.depth.fx, e->calib.depth.fy, e->calib.depth.cx, e->calib.depth.cy);
   tp.termination = settings->termination_threshold;
+  *pyrTotalOut = pyrTotal;
+  return DSR_OK;
+}
+
+}  // namespace
+
+namespace dsr_internal {
+int batch_track_check(const dsr_track_settings *settings) {
+  if (!settings) return fail(DSR_E_ARG, "null settings");
+  return check_settings(settings);
+}
+
+int batch_track(dsr_engine *src, dsr_engine *const *vols, int n, const dsr_track_settings *settings, BatchTrackerDev **btp,
+                dsr_track_result *out) {
+  if (n <= 0) return DSR_OK;
+  if (!*btp) {
+    BatchTrackerDev *nb = new (std::nothrow) BatchTrackerDev();
+    if (!nb) return fail(DSR_E_NOMEM, "batch tracker");
+    if (hipMalloc(reinterpret_cast<void **>(&nb->tabDev), sizeof(BatchTrackVol) * kBatchTrackMax) != hipSuccess ||
+        hipHostMalloc(reinterpret_cast<void **>(&nb->tabHost), sizeof(BatchTrackVol) * kBatchTrackMax, hipHostMallocDefault) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void **>(&nb->statesDev), sizeof(TrackState) * kBatchTrackMax) != hipSuccess ||
+        hipHostMalloc(reinterpret_cast<void **>(&nb->statesHost), sizeof(TrackState) * kBatchTrackMax, hipHostMallocDefault) != hipSuccess ||
+        hipEventCreateWithFlags(&nb->done, hipEventDisableTiming) != hipSuccess) {
+      batch_tracker_free(nb);
+      return fail(DSR_E_NOMEM, "batch tracker tables");
+    }
+    *btp = nb;
+  }
+  BatchTrackerDev *bt = *btp;
+  if (bt->inFlight) { HIP_TRY(hipStreamSynchronize(src->stream)); bt->inFlight = false; }
+  // every volume's record; the level geometry (sizes, regimes, iterations, coarse split) is the same for all: one image size,
+  // one settings
+  int coarseLo = 0;
+  size_t pyrTotal = 0;
+  for (int k = 0; k < n; ++k) {
+    dsr_engine *e = vols[k];
+    BatchTrackVol &v = bt->tabHost[k];
+    memset(&v, 0, sizeof v);
+    { int st = tracker_setup(e, settings, v.tp, &coarseLo, &pyrTotal); if (st) return st; }
+    TrackerDev *t = e->tracker;
+    v.st = bt->statesDev + k; v.log = t->log; v.pyramid = t->pyramid; v.part = t->part; v.partCnt = t->partCnt;
+    v.M0 = e->M_d; v.invM0 = e->invM_d;
+  }
+  const int L = settings->no_hierarchy_levels, lo = settings->no_icp_run_till_level;
+  const TrackP &tp = bt->tabHost[0].tp;
+  hipStream_t S = src->stream;
+  HIP_TRY(hipMemcpyAsync(bt->tabDev, bt->tabHost, sizeof(BatchTrackVol) * n, hipMemcpyHostToDevice, S));
+  bt->inFlight = true;
+  const BatchTrackVol *tab = bt->tabDev;
+  LAUNCH(src, "batch_track_pyramid", k_batch_track_pyramid, dim3(std::max(div_up((long long)pyrTotal, 256), 1), n), dim3(256), tab,
+         (int)pyrTotal);
+  if (coarseLo < L)
+    LAUNCH(src, "batch_track_coarse", k_batch_track_coarse, dim3(n), dim3(kTrackCoarseThreads), tab, coarseLo, L - 1);
+  for (int l = std::min(coarseLo, L) - 1; l >= lo; --l) {
+    const TrackLevelP &lv = tp.lv[l];
+    if (lv.regime == DSR_TRACK_NONE) continue;
+    const dim3 g(std::max(div_up(lv.chunks, 4), 1), n);
+    for (int it = 0; it < lv.iterations; ++it) {
+      if (lv.regime == DSR_TRACK_BOTH) LAUNCH(src, "batch_track_gh", k_batch_track_gh<kRegimeBoth>, g, dim3(256), tab, l, it);
+      else if (lv.regime == DSR_TRACK_ROTATION) LAUNCH(src, "batch_track_gh", k_batch_track_gh<kRegimeRotation>, g, dim3(256), tab, l, it);
+      else LAUNCH(src, "batch_track_gh", k_batch_track_gh<kRegimeTranslation>, g, dim3(256), tab, l, it);
+      LAUNCH(src, "batch_track_step", k_batch_track_step, dim3(n), dim3(kTrackStepThreads), tab, l, it);
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(bt->statesHost, bt->statesDev, sizeof(TrackState) * n, hipMemcpyDeviceToHost, S));
+  HIP_TRY(hipEventRecord(bt->done, S));
+  HIP_TRY(hipEventSynchronize(bt->done));  // the one host wait, for every volume's pose
+  bt->inFlight = false;
+  for (int k = 0; k < n; ++k) {
+    dsr_engine *e = vols[k];
+    const TrackState &hs = bt->statesHost[k];
+    memcpy(e->M_d.m, hs.M, sizeof e->M_d.m);  // the fused pose is exactly the tracker's (dsr_track does the same)
+    memcpy(e->invM_d.m, hs.invM, sizeof e->invM_d.m);
+    e->tracker->logCount = hs.logCount;
+    if (out) {
+      dsr_track_result &r = out[k];
+      r.iterations = hs.iterations;
+      r.valid_points = hs.lastValid;
+      r.f = hs.lastF;
+      r.had_point_cloud = hs.hadPointCloud;
+      memcpy(r.m, hs.M, sizeof r.m);
+      memcpy(r.inv_m, hs.invM, sizeof r.inv_m);
+    }
+  }
+  return DSR_OK;
+}
+}  // namespace dsr_internal
+
+extern "C" {
+
+int32_t dsr_track_abi_version(void) { return DSR_TRACK_ABI_VERSION; }
+
+void dsr_track_default_settings(dsr_track_settings *out) {
+  if (!out) return;
+  memset(out, 0, sizeof *out);
+  out->no_hierarchy_levels = 5;
+  const int regime[5] = {DSR_TRACK_BOTH, DSR_TRACK_BOTH, DSR_TRACK_ROTATION, DSR_TRACK_ROTATION, DSR_TRACK_ROTATION};
+  for (int l = 0; l < DSR_TRACK_MAX_LEVELS; ++l) {
+    out->tracking_regime[l] = l < 5 ? regime[l] : DSR_TRACK_NONE;
+    out->iterations[l] = 2 + 2 * l;  // upstream: 2 at level 0, + 2 per level
+  }
+  out->no_icp_run_till_level = 0;
+  out->dist_threshold = 0.1f * 0.1f;
+  out->termination_threshold = 1e-3f;
+}
+
+int dsr_track(dsr_engine *e, const dsr_track_settings *settings, dsr_track_result *out) {
+  if (!e || !settings) return fail(DSR_E_ARG, "null");
+  if (e->ownerBatch && dsri_batch_is_live(e->ownerBatch))
+    return fail(DSR_E_ARG, "dsr_track: the volume belongs to a live dsr_batch (tracking inside the batch is not supported)");
+  { int st = check_settings(settings); if (st) return st; }
+  CHECK_E(e);  // queues a deferred tracking render (paired render) first: the maps are the last Prepare's
+  if (!e->hasView) return fail(DSR_E_NO_VIEW, "no view yet");
+  TrackP tp;
+  int coarseLo = 0;
+  size_t pyrTotal = 0;
+  { int st = tracker_setup(e, settings, tp, &coarseLo, &pyrTotal); if (st) return st; }
+  TrackerDev *t = e->tracker;
+  const int L = settings->no_hierarchy_levels, lo = settings->no_icp_run_till_level;
+  if (!t->state) {
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&t->state), sizeof(TrackState)));
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&t->stateHost), sizeof(TrackState), hipHostMallocDefault));
+    HIP_TRY(hipEventCreateWithFlags(&t->done, hipEventDisableTiming));
+  }
 
   { int st = before_fusion(e); if (st) return st; }  // after the view's last writer (pipelined / shared view stream)
   LAUNCH(e, "track_pyramid", k_track_pyramid, dim3(std::max(div_up((long long)pyrTotal, 256), 1)), dim3(256), tp, t->state, t->pyramid,

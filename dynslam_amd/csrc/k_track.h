@@ -85,10 +85,11 @@ __device__ float pyr_px(const float *__restrict__ d0, int W0, int x, int y) {
 template <>
 __device__ __forceinline__ float pyr_px<0>(const float *__restrict__ d0, int W0, int x, int y) { return d0[x + y * W0]; }
 
-// one thread per pixel of levels 1 .. levels-1 (concatenated); block 0 also initialises the state block
-__global__ __launch_bounds__(256) void k_track_pyramid(TrackP tp, TrackState *__restrict__ st, float *__restrict__ pyramid, int total,
-                                                       Mat4 M0, Mat4 invM0) {
-  if (blockIdx.x == 0 && threadIdx.x < 16) {
+// one thread per pixel of levels 1 .. levels-1 (concatenated); block 0 also initialises the state block.  The body of
+// k_track_pyramid and k_batch_track_pyramid (k_batch_track.h): `block` is the pixel block.
+__device__ __forceinline__ void track_pyramid_body(const TrackP &tp, TrackState *__restrict__ st, float *__restrict__ pyramid, int total,
+                                                   const Mat4 &M0, const Mat4 &invM0, int block) {
+  if (block == 0 && threadIdx.x < 16) {
     st->M[threadIdx.x] = M0.m[threadIdx.x];
     st->invM[threadIdx.x] = invM0.m[threadIdx.x];
     if (threadIdx.x == 0) {
@@ -96,7 +97,7 @@ __global__ __launch_bounds__(256) void k_track_pyramid(TrackP tp, TrackState *__
       st->hadPointCloud = tp.icpPose[16] != 0.0f ? 1 : 0;
     }
   }
-  int i = blockIdx.x * 256 + threadIdx.x;
+  int i = block * 256 + threadIdx.x;
   if (i >= total) return;
   const int W0 = tp.lv[0].W;
   int off = 0;
@@ -121,6 +122,10 @@ __global__ __launch_bounds__(256) void k_track_pyramid(TrackP tp, TrackState *__
     i -= n;
     off += n;
   }
+}
+__global__ __launch_bounds__(256) void k_track_pyramid(TrackP tp, TrackState *__restrict__ st, float *__restrict__ pyramid, int total,
+                                                       Mat4 M0, Mat4 invM0) {
+  track_pyramid_body(tp, st, pyramid, total, M0, invM0, blockIdx.x);
 }
 
 // ---- one pixel: computePerPointGH_Depth (regime: 1 rotation, 2 translation, 3 both); v: F, nabla[np], hessian[np(np+1)/2]
@@ -311,13 +316,14 @@ __device__ __forceinline__ void load_pose(const float *src, Mat4 &m) {
   for (int i = 0; i < 16; ++i) m.m[i] = src[i];
 }
 
-// ---- fine levels: chunk partials (one wave per chunk, four per workgroup), then the one-workgroup step
+// ---- fine levels: chunk partials (one wave per chunk, four per workgroup), then the one-workgroup step.  The bodies are shared
+// with the batch kernels (k_batch_track.h): `block` is the chunk block.
 template <int REGIME>
-__global__ __launch_bounds__(256) void k_track_gh(TrackP tp, const TrackState *__restrict__ st, int level, int iter,
-                                                  float *__restrict__ part, int *__restrict__ partCnt) {
+__device__ __forceinline__ void track_gh_body(const TrackP &tp, const TrackState *__restrict__ st, int level, int iter,
+                                              float *__restrict__ part, int *__restrict__ partCnt, int block) {
   if (tp.icpPose[16] == 0.0f || (iter > 0 && st->levelDone)) return;
   const TrackLevelP &L = tp.lv[level];
-  const int chunk = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int chunk = block * 4 + (threadIdx.x >> 6);
   if (chunk >= L.chunks) return;
   Mat4 approx, scenePose;
   load_pose(st->invM, approx);
@@ -334,14 +340,23 @@ __global__ __launch_bounds__(256) void k_track_gh(TrackP tp, const TrackState *_
   if (lane < NV) part[lane * L.chunks + chunk] = mine;
   if (lane == NV) partCnt[chunk] = cnt;
 }
+template <int REGIME>
+__global__ __launch_bounds__(256) void k_track_gh(TrackP tp, const TrackState *__restrict__ st, int level, int iter,
+                                                  float *__restrict__ part, int *__restrict__ partCnt) {
+  track_gh_body<REGIME>(tp, st, level, iter, part, partCnt, blockIdx.x);
+}
 
-__global__ __launch_bounds__(kTrackStepThreads) void k_track_step(TrackP tp, TrackState *__restrict__ st, TrackLog *__restrict__ log,
-                                                                  int level, int iter, float *__restrict__ part,
-                                                                  int *__restrict__ partCnt) {
+__device__ __forceinline__ void track_step_body(const TrackP &tp, TrackState *__restrict__ st, TrackLog *__restrict__ log, int level,
+                                                int iter, float *__restrict__ part, int *__restrict__ partCnt) {
   if (tp.icpPose[16] == 0.0f || (iter > 0 && st->levelDone)) return;
   const TrackLevelP &L = tp.lv[level];
   tree_reduce(part, partCnt, L.chunks, L.chunks, track_nv(L.regime));
   if (threadIdx.x == 0) track_step(st, log, part, L.chunks, L.chunks > 0 ? partCnt[0] : 0, L.regime, level, iter, tp.termination);
+}
+__global__ __launch_bounds__(kTrackStepThreads) void k_track_step(TrackP tp, TrackState *__restrict__ st, TrackLog *__restrict__ log,
+                                                                  int level, int iter, float *__restrict__ part,
+                                                                  int *__restrict__ partCnt) {
+  track_step_body(tp, st, log, level, iter, part, partCnt);
 }
 
 // ---- coarse levels [lo, hi] (hi the coarsest): every iteration in one workgroup, partials in LDS
@@ -363,8 +378,8 @@ __device__ __forceinline__ void coarse_chunks(const TrackP &tp, const TrackLevel
   }
 }
 
-__global__ __launch_bounds__(kTrackCoarseThreads) void k_track_coarse(TrackP tp, TrackState *__restrict__ st, TrackLog *__restrict__ log,
-                                                                      int lo, int hi) {
+// the body of k_track_coarse and k_batch_track_coarse: one workgroup of kTrackCoarseThreads
+__device__ __forceinline__ void track_coarse_body(const TrackP &tp, TrackState *__restrict__ st, TrackLog *__restrict__ log, int lo, int hi) {
   if (tp.icpPose[16] == 0.0f) return;
   __shared__ float part[kTrackVals * kTrackCoarseMaxChunks];
   __shared__ int partCnt[kTrackCoarseMaxChunks];
@@ -390,6 +405,10 @@ __global__ __launch_bounds__(kTrackCoarseThreads) void k_track_coarse(TrackP tp,
       if (done) break;
     }
   }
+}
+__global__ __launch_bounds__(kTrackCoarseThreads) void k_track_coarse(TrackP tp, TrackState *__restrict__ st, TrackLog *__restrict__ log,
+                                                                      int lo, int hi) {
+  track_coarse_body(tp, st, log, lo, hi);
 }
 
 }  // namespace dsr

@@ -227,7 +227,9 @@ class Exchange:
 
 class Batch:
     """The instance volumes of one GPU driven together (`dsr_batch_*`, include/dsr.h "volume batch"): `fuse` = silhouette split,
-    SetPose, Integrate and PrepareNextStep of every listed instance in 2 + 6 launches, `render` = their preview renders in two.
+    SetPose, Integrate and PrepareNextStep of every listed instance in 2 + 6 launches, `fuse_tracked` = the same with ICP
+    tracking between SetPose and Integrate (the tracker of every volume in the same launches), `render` = their preview renders
+    in two.
     `source`: the engine that holds the full frame; `volumes`: 1..8 instance-sized engines on its GPU."""
 
     def __init__(self, source, volumes, api=None):
@@ -257,9 +259,7 @@ class Batch:
         except Exception:
             pass
 
-    def fuse(self, items, want_status=False):
-        """items: [(volume index or -1, copy mask (device pointer, w, h) or None, x0, y0, delete mask (device pointer, w, h) or None,
-        dx0, dy0, camera->object pose (matrix or PoseArg) or None)] in the host's order.  -> per-item status list if asked for."""
+    def _fill(self, items):
         n = len(items)
         if n > len(self._items):
             self._items = (_capi.BatchItem * n)()
@@ -275,8 +275,42 @@ class Batch:
                     C.memmove(it.inv_m, pose.buf, 64)
                 else:
                     it.inv_m[:] = _colmajor(pose).tolist()
+        return n
+
+    def fuse(self, items, want_status=False):
+        """items: [(volume index or -1, copy mask (device pointer, w, h) or None, x0, y0, delete mask (device pointer, w, h) or None,
+        dx0, dy0, camera->object pose (matrix or PoseArg) or None)] in the host's order.  -> per-item status list if asked for."""
+        n = self._fill(items)
         self._check(self.api.batch_fuse(self._h, self._items, n, self._status if want_status else None))
         return list(self._status[:n]) if want_status else None
+
+    def _track_api(self):
+        if not hasattr(self, "_tapi"):
+            self._tapi = _capi.bind_track(self.api.lib, self.api.prefix)
+        if self._tapi is None:
+            raise DsrError(_capi.DSR_E_ARG, f"this backend ({self.api.prefix}*) has no ICP tracker: dsr_batch_fuse_tracked is a "
+                                            "libdsr_hip.so entry point")
+        return self._tapi
+
+    def fuse_tracked(self, items, settings=None, want_status=False):
+        """`fuse` with the reference's ITM refinement (enable_itm_refinement_, InstanceReconstructor.cpp:590-650): every volume
+        with an item is tracked by ICP from its item's pose between SetPose and Integrate, and fused at the tracked pose
+        (dsr_batch_fuse_tracked).  settings: a TrackSettings for every volume (None: upstream's defaults).  -> one result dict
+        per item with the keys of EngineCore.track (None for volume -1); with want_status, (that list, per-item status list)."""
+        t = self._track_api()
+        if settings is None:
+            settings = _capi.TrackSettings()
+            t.track_default_settings(C.byref(settings))
+        n = self._fill(items)
+        res = (_capi.TrackResult * n)()
+        self._check(t.batch_fuse_tracked(self._h, self._items, n, C.byref(settings), res, self._status if want_status else None))
+        out = []
+        for (vol, *_), r in zip(items, res):
+            out.append(None if int(vol) < 0 else
+                       {"iterations": r.iterations, "valid_points": r.valid_points, "f": r.f, "had_point_cloud": bool(r.had_point_cloud),
+                        "m": _from_colmajor(np.ctypeslib.as_array(r.m).copy()),
+                        "inv_m": _from_colmajor(np.ctypeslib.as_array(r.inv_m).copy())})
+        return (out, list(self._status[:n])) if want_status else out
 
     def render(self, items, image_type=_capi.IMAGE_FREECAMERA_COLOUR_FROM_VOLUME):
         """items: [(volume index, object->camera pose (matrix or PoseArg), rgba device pointer or None, depth device pointer or None)]"""

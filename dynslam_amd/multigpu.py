@@ -341,14 +341,27 @@ class ShardedScene:
             self.exchange.x.sync()
 
     # -- fusion -----------------------------------------------------------------------------
-    def step(self, rgba, depth_mm, static_pose, masks):
+    def step(self, rgba, depth_mm, static_pose, masks, refine=None):
         """One frame.  rgba / depth_mm: numpy arrays (host path) or device pointers (ints) of the full
         frame, resident on this rank's GPU; static_pose: camera->world of the static map;
         masks: [(instance k, x0, y0, mask, camera->object pose of k)] for EVERY instance (each rank picks its own);
         `mask` is a bbox-local uint8 numpy array (host: staged and synchronised per call, what the reference's host
         does) or a tuple (device pointer, box_w, box_h) of a mask already in HBM (no copy, no synchronisation).
         Order per rank as on one GPU: cut the instance views out of the full frame, blank them in the static view,
-        fuse (InstanceReconstructor.cpp:238-263,569-700)."""
+        fuse (InstanceReconstructor.cpp:238-263,569-700).
+        refine: the reference's enable_itm_refinement_ (InstanceReconstructor.cpp:590-650) — a TrackSettings, or True for
+        upstream's defaults: every owned instance volume is tracked by ICP from its pose between SetPose and fusion (a batch:
+        Batch.fuse_tracked, the trackers of all its volumes in the same launches; else EngineCore.track per volume) and fused at
+        the tracked pose; -> {instance k: track result dict}.  None: no tracking, returns None."""
+        track_settings = None if refine is None or refine is True else refine
+        results = {} if refine is not None else None
+        if results is not None and self.maps:
+            raise ValueError("refine: instance volumes only (map volumes are fused from the static pose)")
+        if results is not None and self.batch is not None and masks and not all(isinstance(m[3], tuple) for m in masks):
+            # a batch volume is tracked by the batch only (dsr_track refuses it): host masks are staged in HBM first
+            staged = [self.torch.from_numpy(np.ascontiguousarray(m, np.uint8)).to(self.device) for _, _, _, m, _ in masks]
+            self.torch.cuda.current_stream(self.device).synchronize()
+            masks = [(k, x0, y0, (t.data_ptr(), m.shape[1], m.shape[0]), rel) for (k, x0, y0, m, rel), t in zip(masks, staged)]
         if self.maps:  # every owned volume fuses the whole frame from the static pose (configs[1]'s step, per volume)
             for e in self.instances.values():
                 if isinstance(rgba, int):
@@ -367,8 +380,14 @@ class ShardedScene:
         if self.batch is not None and masks and all(isinstance(m[3], tuple) for m in masks):
             # the whole instance side of the frame as one batch call: every cut-out and blanking in the host's order, then pose,
             # fusion and tracking render of every owned instance
-            self.batch.fuse([(self.batch_index.get(k, -1), mask if k in self.batch_index else None, x0, y0, mask, x0, y0,
-                              rel if k in self.batch_index else None) for k, x0, y0, mask, rel in masks])
+            items = [(self.batch_index.get(k, -1), mask if k in self.batch_index else None, x0, y0, mask, x0, y0,
+                      rel if k in self.batch_index else None) for k, x0, y0, mask, rel in masks]
+            if results is None:
+                self.batch.fuse(items)
+            else:
+                for (k, *_), r in zip(masks, self.batch.fuse_tracked(items, track_settings)):
+                    if r is not None:
+                        results[k] = r
             masks = ()
         for k, x0, y0, mask, rel in masks:
             ie = self.instances.get(k)
@@ -387,12 +406,15 @@ class ShardedScene:
                     self.source.remove_silhouette(mask, x0, y0)
             if ie is not None:
                 ie.set_pose_inv_m(rel)
+                if results is not None:
+                    results[k] = ie.track(track_settings)
                 ie.process_frame()
                 ie.prepare()
         if self.owns_static:
             self.static.set_pose_inv_m(static_pose)
             self.static.process_frame()
             self.static.prepare()
+        return results
 
     # -- fused preview ----------------------------------------------------------------------
     def _render(self, eng, pose_m, rgba_ptr, depth_ptr, rgba_t=None, depth_t=None):

@@ -23,7 +23,7 @@ extern "C" {
 #endif
 
 /* the version of THIS header's structs and entry points (independent of DSR_ABI_VERSION) */
-#define DSR_TRACK_ABI_VERSION 1
+#define DSR_TRACK_ABI_VERSION 2  /* 2: dsr_batch_fuse_tracked */
 #define DSR_TRACK_MAX_LEVELS 8
 
 /* upstream's TrackerIterationType, same values */
@@ -72,10 +72,26 @@ void dsr_track_default_settings(dsr_track_settings *out);
  * (dsr_prepare), starting from the engine's pose; the engine's pose becomes the tracked one (the next dsr_process_frame
  * integrates with it).  No-op (had_point_cloud = 0) before the first Prepare that wrote the maps.  The work is queued on the
  * engine's stream; the call returns after ONE host wait, for the final pose.  DSR_E_ARG for bad settings and for a volume of
- * a live dsr_batch (tracking inside the batch is not supported); DSR_E_NO_VIEW before the first view.  `out` may be null. */
+ * a live dsr_batch (a batch tracks its volumes through dsr_batch_fuse_tracked); DSR_E_NO_VIEW before the first view.  `out` may
+ * be null. */
 int dsr_track(dsr_engine *e, const dsr_track_settings *settings, dsr_track_result *out);
 
 /* the evaluations of the last dsr_track on this engine, in order (up to `capacity`; *count: how many there were) */
+/* dsr_batch_fuse with InstanceReconstructor.cpp:590-650's ITM refinement (enable_itm_refinement_): for every listed item in the
+ * host's order the view split (ProcessSilhouette + RemoveSilhouette); for every item with a volume, SetPose(item.inv_m), Track,
+ * Integrate, PrepareNextStep.  One `settings` for every volume (the reference's instance drivers copy the static driver's
+ * ITMLibSettings, InstanceReconstructor.cpp:365).  results (n_items, or NULL): per item what dsr_track returns (volume -1: zeroed).
+ *
+ * Per volume the outcome equals, bit for bit, dsr_view_split_silhouette, dsr_set_pose_inv_m(item.inv_m), dsr_track(settings),
+ * dsr_process_frame, dsr_prepare on the same engine: the result, dsr_track_get_log / dsr_track_get_pyramid of the volume
+ * afterwards, its pose (fusion uses the tracker's M / invM as they are, no re-inversion; without a point cloud, item.inv_m), its
+ * allocation status and its whole state.  The trackers of all volumes run in the same launches (14 with upstream's settings) on
+ * the batch's stream; the call waits on the host ONCE for all their poses, plus the status wait of dsr_batch_fuse when
+ * status_out is given.  Bad settings, bad indices and singular poses are refused (DSR_E_ARG) before anything is queued or any
+ * engine's bookkeeping changes.  dsr_track on a volume of the batch stays refused. */
+int dsr_batch_fuse_tracked(dsr_batch *b, const dsr_batch_item *items, int n_items, const dsr_track_settings *settings,
+                           dsr_track_result *results, int32_t *status_out);
+
 int dsr_track_get_log(dsr_engine *e, dsr_track_log_entry *out, int32_t capacity, int32_t *count);
 
 /* the depth pyramid of the last dsr_track (levels 1 .. no_hierarchy_levels - 1, concatenated; level l is (W >> l) x (H >> l)
