@@ -1250,6 +1250,9 @@ int dsr_batch_create(dsr_engine *source, dsr_engine *const *volumes, int n_volum
   b->device = source->device;
   for (int k = 0; k < n_volumes; ++k) {
     dsr_engine *e = volumes[k];
+    // a tracking render the volume deferred before the batch: queued now, on its own stream or the shared one, so that no later
+    // flush can lay maps of an older camera over the batch's (dsr_engine_share_stream below flushes it too, but only when called)
+    { int st = flush_track_render(e); if (st) { delete b; return st; } }
     if (e->stream != source->stream) {  // one queue for the whole batch
       int st = dsr_engine_share_stream(e, source);
       if (st) { delete b; return st; }

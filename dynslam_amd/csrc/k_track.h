@@ -295,14 +295,23 @@ __device__ __noinline__ void track_step(TrackState *st, TrackLog *log, const flo
     } else {
       cholesky_solve(A, 6, st->nabla, step);
     }
-    float inv[16];
-    apply_delta(st->invM, step, regime, inv);
-    m4_inv(inv, st->M);          // SetInvM
-    pose_coerce<DeviceOps>(st->M);  // Coerce
-    m4_inv(st->M, st->invM);     // GetInvM
-    float len = 0.0f;
-    for (int i = 0; i < 6; i++) len += step[i] * step[i];
-    if (DeviceOps::sqrt(len) / 6 < termination) st->levelDone = 1;
+    bool finite = true;
+    for (int i = 0; i < 6; ++i) finite = finite && (__float_as_uint(step[i]) & 0x7f800000u) != 0x7f800000u;
+    if (!finite) {
+      // a rank-deficient system (a zero pivot: e.g. rotation about the normal of the only plane in view): the step is not
+      // applied, it is logged as +0, the pose stays the evaluation's and the level ends (DESIGN.md D.7 [DEVIATION])
+      for (int i = 0; i < 6; ++i) step[i] = 0.0f;
+      st->levelDone = 1;
+    } else {
+      float inv[16];
+      apply_delta(st->invM, step, regime, inv);
+      m4_inv(inv, st->M);          // SetInvM
+      pose_coerce<DeviceOps>(st->M);  // Coerce
+      m4_inv(st->M, st->invM);     // GetInvM
+      float len = 0.0f;
+      for (int i = 0; i < 6; i++) len += step[i] * step[i];
+      if (DeviceOps::sqrt(len) / 6 < termination) st->levelDone = 1;
+    }
   }
   TrackLog &g = log[st->logCount++];
   g.level = level; g.iteration = iter; g.validPoints = N; g.accepted = accepted;

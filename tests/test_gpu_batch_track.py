@@ -69,7 +69,7 @@ def _assert_tracker_equal(a, b, what):
 
 
 def _drive(monkeypatch, size=(320, 96), sync_status=1, n_vols=3, n_inst=4, frames=6, settings=None, oracle=True, render=False,
-           pair=True, between=False, inst_kw=None):
+           pair=True, between=False, inst_kw=None, check64=False):
     """The batch (fuse_tracked) against twin HIP engines driven per volume and, with `oracle`, against the oracle running the
     reference's loop with the CPU tracker's poses.  Volumes own instances 0, 1, 3, ... (instance 2 lives "elsewhere": only
     blanked here); instance 1 has no detection in frame 2; every item starts from a perturbed pose.  settings None: 3 levels at
@@ -85,6 +85,7 @@ def _drive(monkeypatch, size=(320, 96), sync_status=1, n_vols=3, n_inst=4, frame
         settings = tu.default_settings(no_hierarchy_levels=3)
     sc = StreetScene(W, H, n_instances=n_inst)
     calib = make_calib(*sc.intrinsics(), W, H)
+    calib_intr = sc.intrinsics()
     ikw = dict(INSTANCE, sync_status=sync_status, **(inst_kw or {}))
     vkw = dict(VIEW, sync_status=sync_status)
     bs, bi = _hip(vkw)(calib), [_hip(ikw)(calib) for _ in range(n_vols)]
@@ -101,6 +102,8 @@ def _drive(monkeypatch, size=(320, 96), sync_status=1, n_vols=3, n_inst=4, frame
     out = [(torch.zeros((H * W, 4), dtype=torch.uint8, device=dev), torch.zeros((H * W,), dtype=torch.float32, device=dev))
            for _ in range(n_vols)]
     seen_pc = False
+    twin_scene_m = [None] * n_vols  # the pose of each twin's last Prepare that wrote its maps
+    checked = 0
     for i in range(frames):
         rgba, d, masks = _masks(sc, i, n_inst, skip={(1, 2)})
         assert masks, "the scene must show instances"
@@ -119,8 +122,10 @@ def _drive(monkeypatch, size=(320, 96), sync_status=1, n_vols=3, n_inst=4, frame
         else:
             res, status = batch.fuse_tracked(items, settings), None
         assert len(res) == len(items)
+        for r in res:
+            assert r is None or (np.all(np.isfinite(r["m"])) and np.all(np.isfinite(r["inv_m"]))), f"frame {i}: non-finite pose"
         # --- the per-volume calls on the twins
-        twin, twin_status = {}, {}
+        twin, twin_status, inputs = {}, {}, {}
         for k, x0, y0, m, rel in masks:
             if k not in owned:
                 ps.remove_silhouette(m, x0, y0)
@@ -128,13 +133,19 @@ def _drive(monkeypatch, size=(320, 96), sync_status=1, n_vols=3, n_inst=4, frame
             e = pi[owned[k]]
             ps.split_silhouette(e, m, x0, y0)
             e.set_pose_inv_m(starts[k])
+            if check64:  # the tracker's inputs: the view and the maps of the last Prepare
+                rs = e.dump_render_state()
+                inputs[k] = (e.get_view()[1], rs["points"], rs["normals"], twin_scene_m[owned[k]])
             twin[k] = e.track(settings)
+            assert np.all(np.isfinite(twin[k]["m"])) and np.all(np.isfinite(twin[k]["inv_m"])), f"frame {i}: non-finite pose"
             try:
                 e.process_frame()
                 twin_status[k] = 0
             except DsrError as ex:
                 twin_status[k] = ex.status
             e.prepare()
+            if check64 and e.get_stats().no_visible_blocks > 0:  # (only then: the call consumes the deferred render)
+                twin_scene_m[owned[k]] = e.get_pose()[0]
         # --- the reference's loop on the oracle, poses from the CPU tracker
         if oracle:
             ts = settings if settings is not None else tu.default_settings()
@@ -168,6 +179,14 @@ def _drive(monkeypatch, size=(320, 96), sync_status=1, n_vols=3, n_inst=4, frame
             if sync_status:
                 assert status[j] == twin_status[k], f"frame {i}, volume {v}: status {status[j]} vs {twin_status[k]}"
             _assert_tracker_equal(bi[v], pi[v], f"frame {i}, volume {v}")
+            if check64 and res[j]["had_point_cloud"]:
+                from tests import track_ref64 as r64
+                depth, points, normals, scene_m_v = inputs[k]
+                c = calib_intr
+                stats = r64.check_log(bi[v].track_log(), depth, points, normals, c, scene_m_v, starts[k],
+                                      settings if settings is not None else tu.default_settings(), result=res[j],
+                                      pyramid=bi[v].track_pyramid())
+                checked += stats["tight"]
         vb, vp = bs.get_view(), ps.get_view()
         assert np.array_equal(vb[0], vp[0]) and np.array_equal(vb[1], vp[1]), f"frame {i}: blanked source view"
         last = i == frames - 1
@@ -193,6 +212,7 @@ def _drive(monkeypatch, size=(320, 96), sync_status=1, n_vols=3, n_inst=4, frame
             for e in (bi[1], pi[1]) + ((oi[1],) if oracle else ()):
                 e.reset_scene()
     assert seen_pc, "some frame must have tracked against a point cloud"
+    assert not check64 or checked > 0, "check_log held no step to its tight bound"
     batch.close()
     for e in engines:
         e.close()
@@ -366,3 +386,124 @@ def test_sharded_scene_refine_batch_equals_loop(hip_api, monkeypatch):
                 assert np.array_equal(_bits(x), _bits(y))
     for s in scenes:
         s.close()
+
+
+def test_batch_logs_against_float64_reference(hip_api, monkeypatch):
+    """251 x 83 (odd sizes; the larger shapes exceed the instance volumes' one-workgroup path), two volumes, three levels:
+    every volume's log replayed by check_log (tests/track_ref64.py) on the inputs its per-volume twin tracked, and equal to
+    the twin's bit for bit"""
+    _drive(monkeypatch, size=(251, 83), sync_status=1, n_vols=2, n_inst=3, frames=4, oracle=False, check64=True)
+
+
+def _plane_items(vol_mask, dev):
+    import torch
+    t = torch.from_numpy(vol_mask).to(dev)
+    torch.cuda.synchronize()
+    mk = (t.data_ptr(), vol_mask.shape[1], vol_mask.shape[0])
+    return t, mk
+
+
+def test_batch_degenerate_plane_volume(hip_api, monkeypatch):
+    """one volume of a batch sees a single fronto-parallel plane (rank-deficient in exact arithmetic; the fused maps are nearly
+    so): the pose stays finite, check_log holds, and the batch equals its per-volume twin bit for bit"""
+    import torch
+    from dynslam_amd.engine import Batch, EngineCore, default_settings
+    from tests import analytic_scene as asc
+    from tests import track_ref64 as r64
+    monkeypatch.setenv("DSR_PIPELINED_VIEW", "0")
+    W, H = 320, 96
+    intr = asc.intrinsics(W, H)
+    calib = make_calib(*intr, W, H)
+    surf = asc.plane(5.0)
+    kw = dict(INSTANCE, mu=0.2)
+    srcs = [EngineCore(default_settings(**VIEW), calib) for _ in range(2)]
+    vols = [EngineCore(default_settings(**kw), calib) for _ in range(2)]
+    batch = Batch(srcs[0], [vols[0]])
+    dev = torch.device("cuda", 0)
+    mask = np.ones((H - 20, W - 40), np.uint8)
+    t, mk = _plane_items(mask, dev)
+    I4 = np.eye(4, dtype=np.float32)
+    rgba = np.zeros((H, W, 4), np.uint8)
+    depth, _, _ = asc.render(surf, W, H, intr, I4)
+    settings = tu.default_settings()
+    start = tu.perturb(I4, dt=(0.0, 0.0, 0.02), deg=0.0)
+    for frame, pose in enumerate((I4, start)):
+        for s_ in srcs:
+            s_.set_view_float(rgba, depth)
+        res = batch.fuse_tracked([(0, mk, 20, 10, None, 0, 0, pose)], settings)[0]
+        assert np.all(np.isfinite(res["m"])) and np.all(np.isfinite(res["inv_m"])), res
+        e = vols[1]
+        srcs[1].split_silhouette(e, mask, 20, 10)
+        e.set_pose_inv_m(pose)
+        if frame == 1:
+            rs = e.dump_render_state()
+            inputs = (e.get_view()[1], rs["points"], rs["normals"])
+        twin = e.track(settings)
+        assert np.all(np.isfinite(twin["m"])) and np.all(np.isfinite(twin["inv_m"])), twin
+        e.process_frame()
+        e.prepare()
+        _assert_result_equal(res, twin, f"frame {frame}")
+        _assert_tracker_equal(vols[0], vols[1], f"frame {frame}")
+    stats = r64.check_log(vols[0].track_log(), *inputs, intr, np.eye(4), start, settings, result=res, pyramid=vols[0].track_pyramid())
+    print("degenerate plane volume:", stats)
+    srcs[0].sync()
+    assert_scene_equal(vols[0], vols[1], voxels=True)
+    assert_render_equal(vols[0], vols[1])
+    batch.close()
+    for e in srcs + vols:
+        e.close()
+
+
+def test_batch_takes_over_a_volume_with_a_deferred_render(hip_api, monkeypatch):
+    """A volume that already shares the source's stream and was prepared before the batch existed (its tracking render
+    deferred, paired render): dsr_batch_create queues that render.  Otherwise a later fuse_tracked would queue it AFTER the
+    batch's own render, and the tracker would read maps of the old camera.  Sequence: share_stream, fuse + prepare, Batch,
+    fuse, a call on the source, fuse_tracked — against a twin that took the normal route (no share_stream)."""
+    import torch
+    from dynslam_amd.engine import Batch, EngineCore, default_settings
+    monkeypatch.setenv("DSR_PIPELINED_VIEW", "0")
+    W, H = 320, 96
+    sc = StreetScene(W, H, n_instances=2)
+    calib = make_calib(*sc.intrinsics(), W, H)
+    srcs = [EngineCore(default_settings(**VIEW), calib) for _ in range(2)]
+    vols = [EngineCore(default_settings(**INSTANCE), calib) for _ in range(2)]
+    vols[0].share_stream(srcs[0])
+    dev = torch.device("cuda", 0)
+    keep = []
+
+    def items(i, s_):
+        rgba, d, masks = _masks(sc, i, 1)
+        s_.update_view(rgba, d)
+        k, x0, y0, m, rel = masks[0]
+        t = torch.from_numpy(m).to(dev)
+        keep.append(t)
+        torch.cuda.synchronize()
+        mk = (t.data_ptr(), m.shape[1], m.shape[0])
+        return [(0, mk, x0, y0, mk, x0, y0, rel if i < 3 else tu.perturb(rel))], (rgba, d, m, x0, y0, rel)
+
+    for s_, v in zip(srcs, vols):  # fuse and prepare the volume on its own (frame 0), its tracking render deferred
+        _, (rgba, d, m, x0, y0, rel) = items(0, s_)
+        s_.split_silhouette(v, m, x0, y0)
+        v.set_pose_inv_m(rel)
+        v.process_frame()
+        v.prepare()
+    batches = [Batch(s_, [v]) for s_, v in zip(srcs, vols)]
+    for b, s_ in zip(batches, srcs):
+        b.fuse(items(1, s_)[0])
+        s_.get_stats()
+    out = []
+    for b, s_ in zip(batches, srcs):
+        res = b.fuse_tracked(items(3, s_)[0], tu.default_settings(no_hierarchy_levels=3))[0]
+        assert np.all(np.isfinite(res["m"])) and np.all(np.isfinite(res["inv_m"])), res
+        assert res["had_point_cloud"] and res["iterations"] > 0
+        out.append(res)
+    for s_ in srcs:
+        s_.sync()
+    _assert_result_equal(out[0], out[1], "stale render")
+    _assert_tracker_equal(vols[0], vols[1], "stale render")
+    assert_scene_equal(vols[0], vols[1], voxels=True)
+    assert_render_equal(vols[0], vols[1])
+    for b in batches:
+        b.close()
+    for e in srcs + vols:
+        e.close()

@@ -335,3 +335,53 @@ def test_shim_tracking_controller_track(hip_api, tmp_path):
     assert res["iterations"] > 0
     assert np.array_equal(host_m.view(np.uint32), res["m"].view(np.uint32))
     assert np.array_equal(host_inv.view(np.uint32), res["inv_m"].view(np.uint32))
+
+
+def _analytic(W, H, surfaces, view, start, settings, kw=None):
+    """fuse the exact depth of an analytic scene at the identity, Prepare, then track the view at `view` from `start`: the
+    result equals the CPU restatement bit for bit (_check_against_ref) and its log passes check_log (tests/track_ref64.py) on
+    the engine's own view and maps"""
+    from tests import analytic_scene as asc
+    from tests import track_ref64 as r64
+    intr = asc.intrinsics(W, H)
+    g = EngineCore(default_settings(**dict(SMALL, **(kw or {}))), make_calib(*intr, W, H))
+    I4 = np.eye(4, dtype=np.float32)
+    rgba = np.zeros((H, W, 4), np.uint8)
+    g.set_view_float(rgba, asc.render(surfaces, W, H, intr, I4)[0])
+    g.set_pose_inv_m(I4)
+    g.process_frame()
+    g.prepare()
+    scene_m = g.get_pose()[0]
+    g.set_view_float(rgba, asc.render(surfaces, W, H, intr, view)[0])
+    g.set_pose_inv_m(start)
+    rs = g.dump_render_state()
+    depth = g.get_view()[1]
+    res, log = _check_against_ref(g, scene_m, settings, start)
+    assert np.all(np.isfinite(res["m"])) and np.all(np.isfinite(res["inv_m"])), res
+    stats = r64.check_log(g.track_log(), depth, rs["points"], rs["normals"], intr, scene_m, start, settings,
+                          result=res, pyramid=g.track_pyramid())
+    g.close()
+    return res, log, stats
+
+
+@pytest.mark.parametrize("W,H", [(1024, 512), (1032, 512), (1280, 720), (251, 83)])
+def test_analytic_scene_against_float64_reference(hip_api, W, H):
+    """1024 x 512: level 2 is 128 chunks (the one-workgroup kernel's most); 1032 x 512: 129 (the per-iteration pair at level 2);
+    1280 x 720; 251 x 83 (odd sizes, levels under 256 pixels).  Upstream's settings, the start 5.4 cm / 1 degree off the view."""
+    from tests import analytic_scene as asc
+    view = asc.view_pose()
+    res, log, stats = _analytic(W, H, asc.ROOM, view, tu.perturb(view, deg=1.0), _settings())
+    assert stats["tight"] > 0, stats
+    print(f"{W} x {H}: {stats}")
+
+
+@pytest.mark.parametrize("tilt", [0.0, 0.3], ids=["fronto-parallel", "tilted"])
+def test_degenerate_plane_gives_a_finite_pose(hip_api, tilt):
+    """one plane: a rank-deficient system; a non-finite step is not applied, logged as +0 and ends its level (D.7); the pose
+    stays finite, equal to the CPU restatement bit for bit, and the log passes check_log"""
+    from tests import analytic_scene as asc
+    I4 = np.eye(4, dtype=np.float32)
+    for regime in (None, [_capi.TRACK_ROTATION] * 5):
+        s = _settings() if regime is None else _settings(tracking_regime=regime)
+        res, log, stats = _analytic(320, 96, asc.plane(5.0, tilt), I4, tu.perturb(I4, dt=(0.0, 0.0, 0.02), deg=0.0), s)
+        print(f"tilt {tilt}, regime {regime}: {stats}")

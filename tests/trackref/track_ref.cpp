@@ -232,14 +232,21 @@ int tr_track(int W, int H, const float *depth, const float *points, const float 
           } else {
             cholesky_solve(A, 6, nabla_good, step);
           }
-          float inv[16];
-          apply_delta(invM, step, L.regime, inv);
-          m4_inv(inv, M);
-          pose_coerce<HostOps>(M);
-          m4_inv(M, invM);
-          float len = 0.0f;
-          for (int i = 0; i < 6; i++) len += step[i] * step[i];
-          if (sqrtf(len) / 6 < s->termination_threshold) stop = true;
+          bool finite = true;
+          for (int i = 0; i < 6; ++i) finite = finite && std::isfinite(step[i]);
+          if (!finite) {  // a rank-deficient system: no step, logged as +0, the pose kept, the level ends
+            for (int i = 0; i < 6; ++i) step[i] = 0.0f;
+            stop = true;
+          } else {
+            float inv[16];
+            apply_delta(invM, step, L.regime, inv);
+            m4_inv(inv, M);
+            pose_coerce<HostOps>(M);
+            m4_inv(M, invM);
+            float len = 0.0f;
+            for (int i = 0; i < 6; i++) len += step[i] * step[i];
+            if (sqrtf(len) / 6 < s->termination_threshold) stop = true;
+          }
         }
         if (log && nlog < log_cap) {
           dsr_track_log_entry &g = log[nlog];
