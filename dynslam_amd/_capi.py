@@ -285,3 +285,68 @@ def bind_track(lib, prefix):
     if ns.track_abi_version() != TRACK_ABI_VERSION:
         raise ImportError("tracker ABI version mismatch (include/dsr_track.h)")
     return ns
+
+
+# ---- include/dsr_eval.h: LIDAR-vs-depth accuracy scoring.  A table of its own, like the tracker's (the oracle has no evaluator).
+EVAL_ABI_VERSION = 1  # == DSR_EVAL_ABI_VERSION
+EVAL_MAX_CONFIGS = 32
+EVAL_ARG_DETECTIONS = 32
+EVAL_REFERENCE_CONFIGS = 14
+EVAL_NEGATIVE_DISPARITY = 64  # DSR_EVAL_NEGATIVE_DISPARITY
+EVAL_STATIC, EVAL_DYNAMIC, EVAL_SKIP = 0, 1, 2  # dsr_eval_code
+
+
+class EvalCalib(C.Structure):  # dsr_eval_calib
+    _fields_ = [("velo_to_cam", C.c_double * 16), ("proj_left", C.c_double * 12), ("proj_right", C.c_double * 12),
+                ("baseline_m", C.c_float), ("focal_px", C.c_float), ("min_depth_m", C.c_float), ("max_depth_m", C.c_float),
+                ("width", C.c_int32), ("height", C.c_int32)]
+
+
+class EvalDetection(C.Structure):  # dsr_eval_detection
+    _fields_ = [("mask_dev", C.c_void_p), ("x0", C.c_int32), ("y0", C.c_int32), ("box_w", C.c_int32), ("box_h", C.c_int32),
+                ("code", C.c_int32), ("reserved", C.c_int32)]
+
+
+class EvalConfig(C.Structure):  # dsr_eval_config
+    _fields_ = [("delta_max", C.c_float), ("kitti", C.c_int32)]
+
+
+class EvalResult(C.Structure):  # dsr_eval_result (Records.h DepthResult)
+    _fields_ = [("total", C.c_int64), ("error", C.c_int64), ("missing", C.c_int64), ("correct", C.c_int64),
+                ("missing_separate", C.c_int64)]
+
+
+class EvalPart(C.Structure):  # dsr_eval_part
+    _fields_ = [("fused", EvalResult), ("input", EvalResult)]
+
+
+class EvalCounts(C.Structure):  # dsr_eval_counts
+    _fields_ = [("valid", C.c_int64), ("skipped", C.c_int64), ("epipolar", C.c_int64), ("negative_disparity", C.c_int64),
+                ("config", (EvalPart * 2) * EVAL_MAX_CONFIGS)]
+
+
+assert (C.sizeof(EvalCalib), C.sizeof(EvalDetection), C.sizeof(EvalConfig), C.sizeof(EvalCounts)) == (344, 32, 8, 5152)
+
+_EVAL_ARGS = [C.c_int, _P, _P, C.c_int64, _P, _P, C.POINTER(EvalCalib), C.POINTER(EvalDetection), C.c_int32,
+              C.POINTER(EvalConfig), C.c_int32, _P]
+EVAL_SIGNATURES = {
+    "eval_abi_version": (C.c_int32, []),
+    "eval_reference_configs": (C.c_int32, [C.POINTER(EvalConfig)]),
+    "eval_lidar_dev": (C.c_int, _EVAL_ARGS),
+    "eval_lidar": (C.c_int, _EVAL_ARGS + [C.POINTER(EvalCounts)]),
+}
+
+
+def bind_eval(lib, prefix):
+    """The evaluator's entry points `prefix + name` in `lib`, or None when the library has none (the CPU oracle)."""
+    if not hasattr(lib, prefix + "eval_lidar"):
+        return None
+    ns = SimpleNamespace()
+    for name, (res, args) in EVAL_SIGNATURES.items():
+        fn = getattr(lib, prefix + name)
+        fn.restype = res
+        fn.argtypes = args
+        setattr(ns, name, fn)
+    if ns.eval_abi_version() != EVAL_ABI_VERSION:
+        raise ImportError("evaluator ABI version mismatch (include/dsr_eval.h)")
+    return ns

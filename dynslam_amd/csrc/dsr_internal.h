@@ -6,6 +6,7 @@
 //   dsr_hostio.hip    host-side I/O of the boundary: precomputed depth / disparity files, page-locking of the host's buffers
 //   dsr_profile.hip   HIP-event profile read-out, the division self-tests, the HBM copy probe
 //   dsr_track.hip     the ICP depth tracker (include/dsr_track.h): its buffers, the launch sequence of one dsr_track, the read-back
+//   dsr_eval.hip      LIDAR-vs-depth accuracy scoring (include/dsr_eval.h): argument checks, the one launch, the read-back
 // Every kernel header (k_*.h) is included by exactly ONE of them: kernels have external linkage.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -466,6 +466,20 @@ class ShardedScene:
         ex.composite_into(self.target_rgba, self.target_depth, track_id_of_instance, tint_strength, dim_background)
         return self.target_rgba, self.target_depth
 
+    def evaluate_lidar(self, evaluator, points, input_depth_mm, detections=(), frame_idx=-1, sync=True):
+        """The reference's per-frame accuracy metric (Evaluation::EvaluateFrameSeparate) on rank 0's last composited preview
+        target, on the device: `evaluator` is a dynslam_amd.evaluation.LidarEvaluator of this GPU, points / input_depth_mm /
+        detections as its evaluate() takes them.  Queued after preview()'s composite in stream order, as preview orders its own
+        steps: on torch's current stream (where the composite runs), or on the exchange's stream with the native exchange.
+        sync: -> FrameScores (one host wait); else -> the counts tensor, to be read with evaluator.read() after the stream ran.
+        Other ranks: None."""
+        if self.rank != 0:
+            return None
+        stream = self.exchange.x.stream(0) if self.native else None
+        if sync:
+            return evaluator.evaluate(points, self.target_depth, input_depth_mm, detections, frame_idx=frame_idx, stream=stream)
+        return evaluator.evaluate_dev(points, self.target_depth, input_depth_mm, detections, stream=stream)
+
     def _preview_native(self, static_pose_m, instance_pose_m, track_id_of_instance, tint_strength, dim_background):
         """The same preview through `dsr_exchange_*`: renders straight into the exchange's slots, ONE RCCL all-gather issued by the
         library, the composite over the exchange's own target on rank 0 — every ordering (engine streams, exchange stream) is
