@@ -287,6 +287,39 @@ def bind_track(lib, prefix):
     return ns
 
 
+# ---- include/dsr_gc.h: the voxel GC of a batch's volumes.  A table of its own, like the tracker's (the oracle has no batch).
+GC_ABI_VERSION = 1  # == DSR_GC_ABI_VERSION
+
+
+class BatchGcItem(C.Structure):  # dsr_batch_gc_item
+    _fields_ = [("volume", C.c_int32), ("max_weight", C.c_int32), ("min_age", C.c_int32), ("force_all_voxels", C.c_int32)]
+
+
+assert C.sizeof(BatchGcItem) == 16
+
+GC_SIGNATURES = {
+    "gc_abi_version": (C.c_int32, []),
+    "batch_decay": (C.c_int, [_P, C.POINTER(BatchGcItem), C.c_int]),
+    "gc_debug_alloc_list": (C.c_int, [_H, _P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "gc_debug_fifo": (C.c_int, [_H, C.POINTER(C.c_int32)]),
+}
+
+
+def bind_gc(lib, prefix):
+    """The batch GC's entry points `prefix + name` in `lib`, or None when the library has none (the CPU oracle)."""
+    if not hasattr(lib, prefix + "batch_decay"):
+        return None
+    ns = SimpleNamespace()
+    for name, (res, args) in GC_SIGNATURES.items():
+        fn = getattr(lib, prefix + name)
+        fn.restype = res
+        fn.argtypes = args
+        setattr(ns, name, fn)
+    if ns.gc_abi_version() != GC_ABI_VERSION:
+        raise ImportError("batch GC ABI version mismatch (include/dsr_gc.h)")
+    return ns
+
+
 # ---- include/dsr_eval.h: LIDAR-vs-depth accuracy scoring.  A table of its own, like the tracker's (the oracle has no evaluator).
 EVAL_ABI_VERSION = 1  # == DSR_EVAL_ABI_VERSION
 EVAL_MAX_CONFIGS = 32

@@ -21,7 +21,9 @@ using namespace dsr_internal;
 #include "k_mesh.h"
 #include "k_small.h"
 #include "k_batch.h"
+#include "k_batch_gc.h"
 #include "../../include/dsr_track.h"
+#include "../../include/dsr_gc.h"
 
 // the volume batch's deferred work (paired render; defined with dsr_batch below, inside its extern "C" block)
 extern "C" {
@@ -1510,6 +1512,105 @@ int dsr_batch_render(dsr_batch *b, int type, const dsr_batch_render_item *items,
   LAUNCH(src, "batch_raycast_render", k_batch_raycast_render, dim3(div_up(src->W, 16), div_up(src->H, 16), nv), dim3(256),
          frames, (const BatchVolP *)b->volsDev);
   HIP_TRY(hipGetLastError());
+  return DSR_OK;
+}
+
+// ---- the voxel GC of the batch's volumes (include/dsr_gc.h, k_batch_gc.h) ----------------------------------------------------
+
+int32_t dsr_gc_abi_version(void) { return DSR_GC_ABI_VERSION; }
+
+// instance_driver.Decay() after FuseFrame (InstanceReconstructor.cpp:676-678) and track.ReapReconstruction() (:327-338) of every
+// listed volume: per item what dsr_decay does — the same bookkeeping on the host, statement for statement — in 1 or 3 launches
+// for all of them.  Stages: checks, deferred render, FIFO rings, per-volume bookkeeping + this call's table, launches.
+int dsr_batch_decay(dsr_batch *b, const dsr_batch_gc_item *items, int n_items) {
+  if (!b || !dsri_batch_is_live(b)) return fail(DSR_E_ARG, "dsr_batch_decay: null or destroyed batch");
+  if (n_items < 0 || (n_items > 0 && !items)) return fail(DSR_E_ARG, "bad batch arguments");
+  if (n_items == 0) return DSR_OK;
+  dsr_engine *src = b->source;
+  const int nv = (int)b->vols.size();
+  bool listed[kBatchMax] = {};
+  bool anyProcess = false;
+  for (int i = 0; i < n_items; ++i) {  // everything is checked BEFORE anything is queued or any engine's bookkeeping changes
+    const dsr_batch_gc_item &it = items[i];
+    if (it.volume < 0 || it.volume >= nv) return fail(DSR_E_ARG, "bad batch volume index");
+    if (listed[it.volume]) return fail(DSR_E_ARG, "a volume appears twice in one GC call");
+    if (it.min_age < 0) return fail(DSR_E_ARG, "negative min_age");
+    listed[it.volume] = true;
+    anyProcess = anyProcess || it.force_all_voxels || b->vols[it.volume]->fifoLen + 1 > it.min_age;
+  }
+  CHECK_E_NOFLUSH(src);
+  int st = DSR_OK;
+  // the deferred tracking render reads the voxels and the live lists a pass rewrites: it goes first.  A call that only queues
+  // lists reads the live list's ids and writes FIFO planes — nothing the render touches — and leaves it pending (dsr_gc.h)
+  if (anyProcess && (st = engine_flush_deferred(src))) return st;
+  for (int i = 0; i < n_items; ++i) {  // the rings, before the first launch (growing one may fail, and may wait: ensure_fifo)
+    dsr_engine *e = b->vols[items[i].volume];
+    if (!items[i].force_all_voxels && (st = ensure_fifo(e, std::max(items[i].min_age + 1, e->fifoLen + 1)))) return st;
+  }
+  BatchGc g;
+  memset(&g, 0, sizeof g);
+  int maxBlocks = 0;
+  for (int i = 0; i < n_items; ++i) {
+    const dsr_batch_gc_item &it = items[i];
+    dsr_engine *e = b->vols[it.volume];
+    e->sceneVersion++;
+    e->noVisibleValid = false;
+    e->listVersion++;
+    if (e->sidePending) { HIP_TRY(hipStreamWaitEvent(src->stream, e->evExpected, 0)); e->sidePending = false; }
+    BatchGcItemP &o = g.it[i];
+    o.volume = it.volume;
+    o.maxWeight = it.max_weight;
+    const float muv = e->s.mu;  // (dsr_decay's zeroIsReset)
+    o.zeroIsReset = (((-1.0f > muv) || (fabsf(-1.0f / muv) > 0.25f)) && e->s.max_w >= 1) ? 1 : 0;
+    o.cand = e->decayCand; o.flags = e->decayFlags;
+    o.visibleIDs = e->live.visibleIDs; o.visBlocks = e->live.visBlocks; o.visType = e->live.visType;
+    if (it.force_all_voxels) {
+      o.mode = GC_REAP;
+    } else {  // the ring arithmetic of dsr_decay
+      const int slot = (e->fifoHead + e->fifoLen) % e->fifoCap;
+      o.pushPlane = e->fifoPlanes + (size_t)slot * e->fifoPlaneWords;
+      o.planeWords = (int)e->fifoPlaneWords;
+      e->fifoLen++;
+      if (e->fifoLen <= it.min_age) o.mode = GC_PUSH;
+      else {
+        o.mode = GC_POP;
+        o.popPlane = e->fifoPlanes + (size_t)e->fifoHead * e->fifoPlaneWords;
+        e->fifoHead = (e->fifoHead + 1) % e->fifoCap;
+        e->fifoLen--;
+      }
+    }
+    if (o.mode != GC_PUSH) maxBlocks = std::max(maxBlocks, e->noBlocks);
+  }
+  LAUNCH(src, "batch_gc_candidates", k_batch_gc_candidates, dim3(n_items), dim3(kSmallThreads), g, (const BatchVolP *)b->volsDev);
+  if (anyProcess) {
+    // a wave per candidate block and few blocks per wave, as k_decay_blocks runs them (an instance volume has a few thousand)
+    const int grid = std::max(1, std::min(512, div_up(maxBlocks, 4)));
+    LAUNCH(src, "batch_gc_blocks", k_batch_gc_blocks, dim3(grid, n_items), dim3(256), g, (const BatchVolP *)b->volsDev);
+    LAUNCH(src, "batch_gc_commit", k_batch_gc_commit, dim3(n_items), dim3(kSmallThreads), g, (const BatchVolP *)b->volsDev);
+  }
+  HIP_TRY(hipGetLastError());
+  return DSR_OK;
+}
+
+int dsr_gc_debug_alloc_list(dsr_engine *e, int32_t *ids_out, int32_t capacity, int32_t *n, int32_t *valid) {
+  CHECK_E(e);
+  if (!n || !valid || capacity < 0 || (capacity > 0 && !ids_out)) return fail(DSR_E_ARG, "bad arguments");
+  if (!e->scene.allocIds || !e->smallLists) return fail(DSR_E_ARG, "this engine keeps no sorted list of allocated entries");
+  int32_t c[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(c, e->scene.ctr + CTR_NO_ALLOC_IDS, sizeof c, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  *n = c[0]; *valid = c[1];
+  const int m = std::min(std::min(c[0], capacity), e->noBlocks);
+  if (m > 0) {
+    HIP_TRY(hipMemcpyAsync(ids_out, e->scene.allocIds, (size_t)m * 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+  }
+  return DSR_OK;
+}
+
+int dsr_gc_debug_fifo(dsr_engine *e, int32_t out[3]) {
+  if (!e || !out) return fail(DSR_E_ARG, "bad arguments");
+  out[0] = e->fifoHead; out[1] = e->fifoLen; out[2] = e->fifoCap;
   return DSR_OK;
 }
 

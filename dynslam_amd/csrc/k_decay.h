@@ -115,14 +115,13 @@ __global__ __launch_bounds__(kTileThreads) void k_bits_write(const uint8_t *__re
 // (sdf 32767, no colour) — true whenever colour can only be fused together with depth (mu < 4 m:
 // voxels the depth step rejects never pass the colour gate) and max_w >= 1 —, so resetting it
 // again would only rewrite the same bytes: such voxels count as empty but are not touched.
-__global__ __launch_bounds__(256) void k_decay_blocks(SceneP s, const int32_t *__restrict__ cand,
-                                                      const int32_t *__restrict__ nCandPtr, int maxWeight,
-                                                      uint8_t *__restrict__ freedFlag, int zeroIsReset) {
-  const int n = *nCandPtr;
-  if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&s.work[WORK_V_DECAY], (unsigned long long)n);
+// (the body, by workgroup `wg` of `nWg` workgroups of 256 threads: the kernel below, or one volume's share of k_batch_gc_blocks)
+__device__ __forceinline__ void decay_blocks_body(const SceneP &s, const int32_t *__restrict__ cand, int n, int maxWeight,
+                                                  uint8_t *__restrict__ freedFlag, int zeroIsReset, int wg, int nWg) {
+  if (wg == 0 && threadIdx.x == 0) atomicAdd(&s.work[WORK_V_DECAY], (unsigned long long)n);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  for (int i = blockIdx.x * 4 + wave; i < n; i += gridDim.x * 4) {
+  for (int i = wg * 4 + wave; i < n; i += nWg * 4) {
     const int t = __builtin_amdgcn_readfirstlane(cand[i]);
     const int ptr = s.table[t].ptr;
     if (ptr < 0) { if (lane == 0) freedFlag[i] = 0; continue; }
@@ -165,6 +164,11 @@ __global__ __launch_bounds__(256) void k_decay_blocks(SceneP s, const int32_t *_
     for (int d = 32; d >= 1; d >>= 1) empty += __shfl_xor(empty, d);
     if (lane == 0) freedFlag[i] = (empty == kBlockSize3) ? 1 : 0;
   }
+}
+__global__ __launch_bounds__(256) void k_decay_blocks(SceneP s, const int32_t *__restrict__ cand,
+                                                      const int32_t *__restrict__ nCandPtr, int maxWeight,
+                                                      uint8_t *__restrict__ freedFlag, int zeroIsReset) {
+  decay_blocks_body(s, cand, *nCandPtr, maxWeight, freedFlag, zeroIsReset, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // ordered prefix over the candidate list's freed flags

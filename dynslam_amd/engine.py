@@ -312,6 +312,26 @@ class Batch:
                         "inv_m": _from_colmajor(np.ctypeslib.as_array(r.inv_m).copy())})
         return (out, list(self._status[:n])) if want_status else out
 
+    def _gc_api(self):
+        if not hasattr(self, "_gapi"):
+            self._gapi = _capi.bind_gc(self.api.lib, self.api.prefix)
+        if self._gapi is None:
+            raise DsrError(_capi.DSR_E_ARG, f"this backend ({self.api.prefix}*) has no batch GC: dsr_batch_decay is a "
+                                            "libdsr_hip.so entry point")
+        return self._gapi
+
+    def decay(self, items):
+        """The voxel GC of the listed volumes in the same launches (dsr_batch_decay, include/dsr_gc.h): per item, in order, what
+        EngineCore.decay(max_weight, min_age, force_all) does on that volume — instance_driver.Decay() after FuseFrame
+        (InstanceReconstructor.cpp:676-678), or with force_all the track's Reap (:327-338).
+        items: [(volume index, max_weight, min_age, force_all)]; a volume at most once per call."""
+        g = self._gc_api()
+        n = len(items)
+        arr = (_capi.BatchGcItem * max(n, 1))()
+        for it, (vol, max_weight, min_age, force_all) in zip(arr, items):
+            it.volume, it.max_weight, it.min_age, it.force_all_voxels = int(vol), int(max_weight), int(min_age), int(bool(force_all))
+        self._check(g.batch_decay(self._h, arr, n))
+
     def render(self, items, image_type=_capi.IMAGE_FREECAMERA_COLOUR_FROM_VOLUME):
         """items: [(volume index, object->camera pose (matrix or PoseArg), rgba device pointer or None, depth device pointer or None)]"""
         n = len(items)
@@ -530,6 +550,28 @@ class EngineCore:
 
     def decay(self, max_weight, min_age, force_all_voxels=False):
         self._check(self.api.decay(self._h, int(max_weight), int(min_age), int(bool(force_all_voxels))))
+
+    def _gc_api(self):
+        if not hasattr(self, "_gapi"):
+            self._gapi = _capi.bind_gc(self.api.lib, self.api.prefix)
+        if self._gapi is None:
+            raise DsrError(_capi.DSR_E_ARG, f"this backend ({self.api.prefix}*) has no include/dsr_gc.h entry points")
+        return self._gapi
+
+    def debug_alloc_list(self):
+        """For tests (dsr_gc_debug_alloc_list): -> (valid, ids) — the sorted list of allocated entries of an instance-sized volume
+        as the device holds it."""
+        g = self._gc_api()
+        ids = np.zeros(max(self.no_blocks, 1), np.int32)
+        n, valid = C.c_int32(0), C.c_int32(0)
+        self._check(g.gc_debug_alloc_list(self._h, _ptr(ids), len(ids), C.byref(n), C.byref(valid)))
+        return bool(valid.value), ids[:min(n.value, len(ids))].copy()
+
+    def debug_fifo(self):
+        """For tests (dsr_gc_debug_fifo): -> (head, length, capacity) of the voxel GC's FIFO of visible lists, host side."""
+        out = (C.c_int32 * 3)()
+        self._check(self._gc_api().gc_debug_fifo(self._h, out))
+        return tuple(out)
 
     # -- rendering ----------------------------------------------------------
     def get_image(self, image_type, pose_m=None, intrinsics=None, want_rgba=True, want_depth=False):

@@ -258,9 +258,12 @@ class ShardedScene:
     """
 
     def __init__(self, make_engine, width, height, n_volumes, world_size, rank, device, group=None, local_only=False,
-                 has_static=True, share_streams=True, use_batch=True, maps=False):
+                 has_static=True, share_streams=True, use_batch=True, maps=False, voxel_decay_params=None):
         import torch
         self.torch = torch
+        # the reference's voxel GC of the instance volumes (use_decay_ = the static driver's IsDecayEnabled(), DynSlam.h:48-52):
+        # a dynslam_amd.engine.VoxelDecayParams; None or enabled=False: no Decay in step(), as before
+        self.voxel_decay_params = voxel_decay_params if voxel_decay_params is not None and voxel_decay_params.enabled else None
         self.W, self.H, self.P = int(width), int(height), int(width) * int(height)
         self.world, self.rank, self.device = int(world_size), int(rank), device
         self.n_volumes = int(n_volumes)
@@ -352,7 +355,10 @@ class ShardedScene:
         refine: the reference's enable_itm_refinement_ (InstanceReconstructor.cpp:590-650) — a TrackSettings, or True for
         upstream's defaults: every owned instance volume is tracked by ICP from its pose between SetPose and fusion (a batch:
         Batch.fuse_tracked, the trackers of all its volumes in the same launches; else EngineCore.track per volume) and fused at
-        the tracked pose; -> {instance k: track result dict}.  None: no tracking, returns None."""
+        the tracked pose; -> {instance k: track result dict}.  None: no tracking, returns None.
+        With voxel_decay_params: instance_driver.Decay() after the fusion of every owned instance that had a detection
+        (InstanceReconstructor.cpp:676-678) — Batch.decay for the volumes of a batch, EngineCore.decay in the loop."""
+        vd = self.voxel_decay_params
         track_settings = None if refine is None or refine is True else refine
         results = {} if refine is not None else None
         if results is not None and self.maps:
@@ -388,6 +394,10 @@ class ShardedScene:
                 for (k, *_), r in zip(masks, self.batch.fuse_tracked(items, track_settings)):
                     if r is not None:
                         results[k] = r
+            if vd is not None:
+                gc = [(self.batch_index[k], vd.max_decay_weight, vd.min_decay_age, False) for k, *_ in masks if k in self.batch_index]
+                if gc:
+                    self.batch.decay(gc)
             masks = ()
         for k, x0, y0, mask, rel in masks:
             ie = self.instances.get(k)
@@ -410,11 +420,25 @@ class ShardedScene:
                     results[k] = ie.track(track_settings)
                 ie.process_frame()
                 ie.prepare()
+                if vd is not None:
+                    ie.decay(vd.max_decay_weight, vd.min_decay_age, False)
         if self.owns_static:
             self.static.set_pose_inv_m(static_pose)
             self.static.process_frame()
             self.static.prepare()
         return results
+
+    def reap(self, instance_ids, max_weight):
+        """track.ReapReconstruction() of the listed instances (InstanceReconstructor.cpp:327-338: a track with a gap of two frames
+        or more; Track.h:222-229 -> InfiniTamDriver::Reap = Decay(max_weight, 0, forceAllVoxels)): every rank reaps the ones it
+        owns — the volumes of a batch in one Batch.decay call, else EngineCore.decay per volume."""
+        mine = [k for k in dict.fromkeys(instance_ids) if k in self.instances]
+        if self.batch is not None:
+            if mine:
+                self.batch.decay([(self.batch_index[k], max_weight, 0, True) for k in mine])
+            return
+        for k in mine:
+            self.instances[k].decay(max_weight, 0, True)
 
     # -- fused preview ----------------------------------------------------------------------
     def _render(self, eng, pose_m, rgba_ptr, depth_ptr, rgba_t=None, depth_t=None):
