@@ -383,3 +383,46 @@ def bind_eval(lib, prefix):
     if ns.eval_abi_version() != EVAL_ABI_VERSION:
         raise ImportError("evaluator ABI version mismatch (include/dsr_eval.h)")
     return ns
+
+
+# ---- include/dsr_snapshot.h: save / restore of an engine's complete state.  A table of its own, like the tracker's (the oracle has
+# no snapshot).
+SNAPSHOT_ABI_VERSION = 1  # == DSR_SNAPSHOT_ABI_VERSION
+SNAPSHOT_FORMAT_VERSION = 1  # == DSR_SNAPSHOT_FORMAT_VERSION
+
+
+class SnapshotInfo(C.Structure):  # struct dsr_snapshot_info
+    _fields_ = [("format_version", C.c_uint32), ("voxel_size", C.c_float), ("mu", C.c_float), ("max_w", C.c_int32),
+                ("hash_bucket_num", C.c_int32), ("excess_list_size", C.c_int32), ("sdf_local_block_num", C.c_int32),
+                ("width", C.c_int32), ("height", C.c_int32), ("rgb_width", C.c_int32), ("rgb_height", C.c_int32),
+                ("use_swapping", C.c_int32), ("depth_weighting", C.c_int32), ("n_sections", C.c_uint32), ("section_mask", C.c_uint32),
+                ("_pad", C.c_uint32), ("owned_blocks", C.c_uint64), ("total_bytes", C.c_uint64), ("payload_bytes", C.c_uint64),
+                ("reserved", C.c_uint64 * 4)]
+
+
+assert C.sizeof(SnapshotInfo) == 120
+
+SNAPSHOT_SIGNATURES = {
+    "snapshot_abi_version": (C.c_int32, []),
+    "snapshot_save": (C.c_int, [_H, C.c_char_p]),
+    "snapshot_load": (C.c_int, [_H, C.c_char_p]),
+    "snapshot_export": (C.c_int, [_H, C.POINTER(C.c_void_p)]),
+    "snapshot_import": (C.c_int, [_H, C.c_void_p]),
+    "snapshot_free": (None, [C.c_void_p]),
+    "snapshot_info": (C.c_int, [C.c_char_p, C.c_void_p, C.POINTER(SnapshotInfo)]),
+}
+
+
+def bind_snapshot(lib, prefix):
+    """The snapshot entry points `prefix + name` in `lib`, or None when the library has none (the CPU oracle)."""
+    if not hasattr(lib, prefix + "snapshot_save"):
+        return None
+    ns = SimpleNamespace()
+    for name, (res, args) in SNAPSHOT_SIGNATURES.items():
+        fn = getattr(lib, prefix + name)
+        fn.restype = res
+        fn.argtypes = args
+        setattr(ns, name, fn)
+    if ns.snapshot_abi_version() != SNAPSHOT_ABI_VERSION:
+        raise ImportError("snapshot ABI version mismatch (include/dsr_snapshot.h)")
+    return ns

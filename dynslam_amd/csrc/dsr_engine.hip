@@ -497,6 +497,26 @@ int dsr_internal::engine_flush_deferred(dsr_engine *e) {
   return DSR_OK;
 }
 void dsr_internal::engine_prof_resolve(dsr_engine *e) { prof_resolve(e); }
+// ---- for dsr_snapshot.hip (include/dsr_snapshot.h): the engine's own steps a snapshot is built from
+int dsr_internal::engine_reset(dsr_engine *e) { return reset_scene(e); }
+int dsr_internal::engine_list_allocated(dsr_engine *e) {
+  // the ascending list of the allocated entries, as Decay(forceAllVoxels) and meshing build it
+  LAUNCH(e, "snapshot_candidates", k_allocated_count, dim3(e->numTilesE), dim3(kTileThreads), e->scene, e->E, e->tileSums);
+  LAUNCH(e, "scan_tiles", k_scan_tile_sums, dim3(1), dim3(1024), e->tileSums, e->numTilesE, e->scene, (int)SCAN_NCAND, e->noBlocks);
+  LAUNCH(e, "snapshot_candidates", k_allocated_write, dim3(e->numTilesE), dim3(kTileThreads), e->scene, e->E,
+         (const int2 *)e->tileSums, e->decayCand, e->noBlocks);
+  HIP_TRY(hipGetLastError());
+  return DSR_OK;
+}
+int dsr_internal::engine_ensure_fifo(dsr_engine *e, int slots) { return ensure_fifo(e, slots); }
+int dsr_internal::engine_add_host_slab(dsr_engine *e) { return add_host_slab(e); }
+int dsr_internal::engine_small_bit_words() { return kSmallBitWords; }
+bool dsr_internal::engine_in_live_batch(dsr_engine *e) {
+  if (!e->ownerBatch) return false;
+  if (dsri_batch_is_live(e->ownerBatch)) return true;
+  e->ownerBatch = nullptr;  // destroyed since
+  return false;
+}
 
 extern "C" {
 

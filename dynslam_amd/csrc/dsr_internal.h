@@ -7,6 +7,7 @@
 //   dsr_profile.hip   HIP-event profile read-out, the division self-tests, the HBM copy probe
 //   dsr_track.hip     the ICP depth tracker (include/dsr_track.h): its buffers, the launch sequence of one dsr_track, the read-back
 //   dsr_eval.hip      LIDAR-vs-depth accuracy scoring (include/dsr_eval.h): argument checks, the one launch, the read-back
+//   dsr_snapshot.hip  save / load / export / import of an engine's complete state (include/dsr_snapshot.h): the file format, pack / unpack
 // Every kernel header (k_*.h) is included by exactly ONE of them: kernels have external linkage.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -331,6 +332,15 @@ extern std::atomic<int> g_enginesOnDevice[64];  // live engines per device (rang
 int engine_set_device(dsr_engine *e);
 int engine_flush_deferred(dsr_engine *e);  // queue what dsr_prepare / dsr_batch_fuse deferred (paired render)
 void engine_prof_resolve(dsr_engine *e);
+// ... for dsr_snapshot.hip: ResetScene; the ascending list of allocated entries into e->decayCand with its length in
+// ctr[CTR_DECAY_NCAND] (the list kernels of Decay(forceAll) and meshing); the GC ring grown to `slots` planes; one more slab of the
+// host store; the words of SceneP::allocBits; is the engine a volume or the source of a batch that is still alive?
+int engine_reset(dsr_engine *e);
+int engine_list_allocated(dsr_engine *e);
+int engine_ensure_fifo(dsr_engine *e, int slots);
+int engine_add_host_slab(dsr_engine *e);
+int engine_small_bit_words();
+bool engine_in_live_batch(dsr_engine *e);
 int engine_render(dsr_engine *e, int type, const float pose_m[16], const float intrinsics[4], void *rgba_out, void *depth_out,
                   bool outIsDevice);
 // dsr_hostio.hip: is [p, p + bytes) inside a range the caller page-locked through dsr_pin_host_buffer?

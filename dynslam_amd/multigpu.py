@@ -290,17 +290,8 @@ class ShardedScene:
                                           "with view_pipeline=VIEW_PIPELINE_OFF to queue the pair on one stream")
         # several instance volumes on this GPU: driven as ONE batch — every kernel of an instance frame launched once for all of
         # them (dsr_batch_*; results identical to the per-volume calls).  Up to 8 per batch; a rank with more keeps the loop.
-        self.batch, self.batch_index = None, {}
-        if self.on_gpu and use_batch and not self.maps and 2 <= len(self.instances) <= 8 and hasattr(self.source.api, "batch_create"):
-            from .engine import Batch
-            order = sorted(self.instances)
-            try:
-                self.batch = Batch(self.source, [self.instances[k] for k in order])
-                self.batch_index = {k: i for i, k in enumerate(order)}
-            except DsrError as ex:  # not batchable (pipelined views, other table sizes): the per-volume loop
-                self.batch = None
-                _log_once("batch", f"ShardedScene: {len(self.instances)} instance volumes are driven one by one, not as a batch ({ex}); "
-                                   "create the engines with view_pipeline=VIEW_PIPELINE_OFF")
+        self.use_batch = bool(use_batch)
+        self._build_batch()
         # GPUs: the C ABI's exchange (RCCL called by the library) whenever RCCL can host the ranks — a process group on "nccl", or a
         # single rank; several ranks on ONE GPU (gloo, tests) and CPU tensors (the oracle, tests) go through torch.distributed
         import torch.distributed as dist
@@ -316,6 +307,108 @@ class ShardedScene:
             self.target_rgba = torch.zeros((self.P, 4), dtype=torch.uint8, device=device)
             self.target_depth = torch.zeros((self.P,), dtype=torch.float32, device=device)
 
+    def _build_batch(self):
+        from .engine import DsrError
+        self.batch, self.batch_index = None, {}
+        if self.on_gpu and self.use_batch and not self.maps and 2 <= len(self.instances) <= 8 and hasattr(self.source.api, "batch_create"):
+            from .engine import Batch
+            order = sorted(self.instances)
+            try:
+                self.batch = Batch(self.source, [self.instances[k] for k in order])
+                self.batch_index = {k: i for i, k in enumerate(order)}
+            except DsrError as ex:  # not batchable (pipelined views, other table sizes, volumes on another GPU): the per-volume loop
+                self.batch = None
+                _log_once("batch", f"ShardedScene: {len(self.instances)} instance volumes are driven one by one, not as a batch ({ex}); "
+                                   "create the engines with view_pipeline=VIEW_PIPELINE_OFF")
+
+    def _drop_batch(self):
+        if self.batch is not None:
+            self.batch.close()
+            self.batch = None
+            self.batch_index = {}
+
+    # -- snapshots (include/dsr_snapshot.h) ---------------------------------------------------
+    def _named_volumes(self):
+        out = {}
+        if self.static is not None:
+            out["static"] = self.static
+        for k, e in self.instances.items():
+            out[f"instance_{k}"] = e
+        if self.source is not None and self.source is not self.static:
+            out["view"] = self.source
+        return out
+
+    def save(self, directory):
+        """Every volume this rank holds as one snapshot file in `directory`, plus a small manifest (manifest_rank<r>.json): what
+        `load` of a scene built with the same arguments needs.  Reads only; the batch stays as it is."""
+        import json
+        import os
+        os.makedirs(directory, exist_ok=True)
+        files = {}
+        for name, e in self._named_volumes().items():
+            files[name] = f"rank{self.rank}_{name}.snap"
+            e.save_snapshot(os.path.join(directory, files[name]))
+        manifest = dict(format=1, rank=self.rank, world_size=self.world, n_volumes=self.n_volumes, has_static=self.has_static, maps=self.maps,
+                        width=self.W, height=self.H, volumes=files)
+        with open(os.path.join(directory, f"manifest_rank{self.rank}.json"), "w") as f:
+            json.dump(manifest, f, indent=1, sort_keys=True)
+        return manifest
+
+    def load(self, directory):
+        """The volumes saved by `save` of a scene with the same layout replace this rank's (the batch is rebuilt around the load: a
+        member of a live batch cannot be loaded into)."""
+        import json
+        import os
+        with open(os.path.join(directory, f"manifest_rank{self.rank}.json")) as f:
+            manifest = json.load(f)
+        mine = self._named_volumes()
+        for key in ("world_size", "n_volumes", "has_static", "maps", "width", "height"):
+            have = dict(world_size=self.world, n_volumes=self.n_volumes, has_static=self.has_static, maps=self.maps, width=self.W, height=self.H)[key]
+            if manifest[key] != have:
+                raise ValueError(f"ShardedScene.load: the saved scene has {key} = {manifest[key]}, this one {have}")
+        if set(manifest["volumes"]) != set(mine):
+            raise ValueError(f"ShardedScene.load: the saved scene holds {sorted(manifest['volumes'])}, this one {sorted(mine)}")
+        self.sync()
+        self._drop_batch()
+        try:
+            for name, e in mine.items():
+                e.load_snapshot(os.path.join(directory, manifest["volumes"][name]))
+        finally:
+            self._build_batch()
+
+    def migrate(self, volume, device):
+        """Move one volume — "static" or an instance id — to an engine created on GPU `device` (an ordinal) with the same settings:
+        export, import, close the old engine.  The batch is rebuilt around the move (volumes of another GPU than the source's are
+        driven one by one).  Results are those of a scene that never moved."""
+        import ctypes
+        from .engine import EngineCore
+        old = self.static if volume == "static" else self.instances[volume]
+        settings = type(old.settings)()
+        ctypes.memmove(ctypes.byref(settings), ctypes.byref(old.settings), ctypes.sizeof(settings))
+        settings.device = int(device)
+        new = EngineCore(settings, old.calib, api=old.api)
+        self.sync()
+        self._drop_batch()
+        try:
+            snap = old.export_snapshot()
+            try:
+                new.import_snapshot(snap)
+            finally:
+                snap.close()
+        except Exception:
+            new.close()
+            self._build_batch()
+            raise
+        if volume == "static":
+            if self.source is self.static:
+                self.source = new
+            self.static = new
+        else:
+            self.instances[volume] = new
+        old.close()
+        self._build_batch()
+        return new
+
     def engines(self):
         out = ([self.static] if self.static is not None else []) + list(self.instances.values())
         if self.source is not None and self.source is not self.static:
@@ -324,9 +417,7 @@ class ShardedScene:
 
     def close(self):
         self.sync()
-        if self.batch is not None:
-            self.batch.close()
-            self.batch = None
+        self._drop_batch()
         if self.native:
             self.exchange.close()
         for e in self.engines():

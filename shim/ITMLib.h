@@ -25,12 +25,16 @@
 
 #include "../include/dsr.h"
 #include "../include/dsr_track.h"
+#include "../include/dsr_snapshot.h"
 
 // The tracker's entry points are referenced WEAKLY: a host linked against a library without them (the CPU oracle's orc_* build
 // of the reference's hosts) still links, and ITMTrackingController::Track then throws as it did before the tracker existed.
 extern "C" {
 int dsr_track(dsr_engine *e, const dsr_track_settings *settings, dsr_track_result *out) __attribute__((weak));
 void dsr_track_default_settings(dsr_track_settings *out) __attribute__((weak));
+// ... and so are the snapshot's (include/dsr_snapshot.h): SaveToFile / LoadFromFile throw on a library without them
+int dsr_snapshot_save(dsr_engine *e, const char *path) __attribute__((weak));
+int dsr_snapshot_load(dsr_engine *e, const char *path) __attribute__((weak));
 }
 
 #ifndef SDF_BLOCK_SIZE
@@ -595,6 +599,22 @@ class ITMMainEngine {
   }
   // ITMMainEngine::SaveSceneToMesh (DynSlam.cpp:188-196)
   void SaveSceneToMesh(const char *objFileName) { ITMLib::Engine::dsr_throw(dsr_save_scene_to_mesh(engine_, objFileName)); }
+  // ITMMainEngine::SaveToFile / LoadFromFile: the names of InfiniTAM v3, BUILDER-DEFINED here (the reference's fork of v2 has no
+  // checkpoint).  The volume's complete state — scene, render states, tracking maps, view, pose — as a snapshot file
+  // (include/dsr_snapshot.h); the loading engine was built with equal settings.  After LoadFromFile the engine's pose is the saved
+  // one, and trackingState->pose_d holds it bit for bit (as after Track).
+  void SaveToFile(const char *fileName) {
+    if (!dsr_snapshot_save) throw std::runtime_error("this library has no snapshot entry points (include/dsr_snapshot.h)");
+    ITMLib::Engine::dsr_throw(dsr_snapshot_save(engine_, fileName));
+  }
+  void LoadFromFile(const char *fileName) {
+    if (!dsr_snapshot_load) throw std::runtime_error("this library has no snapshot entry points (include/dsr_snapshot.h)");
+    ITMLib::Engine::dsr_throw(dsr_snapshot_load(engine_, fileName));
+    Matrix4f m, im;
+    ITMLib::Engine::dsr_throw(dsr_get_pose(engine_, m.m, im.m));
+    trackingState->pose_d->SetFromEngine(m, im);
+    static_cast<ITMRenderState_VH *>(renderState_live)->noVisibleBlocks.invalidate(engine_);
+  }
 
  protected:
   const ITMLibSettings *settings;
