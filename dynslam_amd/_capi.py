@@ -426,3 +426,29 @@ def bind_snapshot(lib, prefix):
     if ns.snapshot_abi_version() != SNAPSHOT_ABI_VERSION:
         raise ImportError("snapshot ABI version mismatch (include/dsr_snapshot.h)")
     return ns
+
+
+# ---- include/dsr_mesh.h: the complete mesh of a swapping engine.  A table of its own, like the snapshot's (the oracle has none).
+MESH_ABI_VERSION = 1  # == DSR_MESH_ABI_VERSION
+
+MESH_SIGNATURES = {
+    "mesh_abi_version": (C.c_int32, []),
+    "mesh_scene_complete": (C.c_int, [_H, C.POINTER(C.c_uint64)]),
+    "save_scene_to_mesh_complete": (C.c_int, [_H, C.c_char_p]),
+    "dump_merged_block": (C.c_int, [_H, C.c_int, _P, C.POINTER(C.c_int)]),
+}
+
+
+def bind_mesh(lib, prefix):
+    """The complete mesher's entry points `prefix + name` in `lib`, or None when the library has none (the CPU oracle)."""
+    if not hasattr(lib, prefix + "mesh_scene_complete"):
+        return None
+    ns = SimpleNamespace()
+    for name, (res, args) in MESH_SIGNATURES.items():
+        fn = getattr(lib, prefix + name)
+        fn.restype = res
+        fn.argtypes = args
+        setattr(ns, name, fn)
+    if ns.mesh_abi_version() != MESH_ABI_VERSION:
+        raise ImportError("complete mesher ABI version mismatch (include/dsr_mesh.h)")
+    return ns

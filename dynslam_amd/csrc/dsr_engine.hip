@@ -19,11 +19,13 @@ using namespace dsr_internal;
 #include "k_raycast.h"
 #include "k_swap.h"
 #include "k_mesh.h"
+#include "k_mesh_complete.h"
 #include "k_small.h"
 #include "k_batch.h"
 #include "k_batch_gc.h"
 #include "../../include/dsr_track.h"
 #include "../../include/dsr_gc.h"
+#include "../../include/dsr_mesh.h"
 
 // the volume batch's deferred work (paired render; defined with dsr_batch below, inside its extern "C" block)
 extern "C" {
@@ -1671,17 +1673,87 @@ int dsr_dump_stored_block(dsr_engine *e, int entry, dsr_voxel *out, int *present
 
 // ---- meshing
 
-int dsr_mesh_free(dsr_engine *e) {
-  CHECK_E(e);
+extern "C++" {  // (templates: this part of the file sits inside the extern "C" block of the ABI)
+namespace {
+int mesh_release(dsr_engine *e) {
   if (e->meshTris) { HIP_TRY(hipStreamSynchronize(e->stream)); (void)hipFree(e->meshTris); e->meshTris = nullptr; }
   e->meshCount = 0;
   return DSR_OK;
 }
 
+// device scratch of one meshing call, freed when the call returns (every kernel that used it has run by then: the calls wait)
+struct MeshScratch {
+  std::vector<void *> bufs;
+  template <class T>
+  int get(T **p, size_t n) {
+    if (hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess)
+      return fail(DSR_E_NOMEM, "mesh scratch allocation failed");
+    bufs.push_back(*p);
+    return DSR_OK;
+  }
+  ~MeshScratch() { for (void *b : bufs) (void)hipFree(b); }
+};
+
+// Marching cubes over the ordered list of n entries (its length on the device: *nPtr), in chunks of `chunk` entries: count per
+// block, scan, write.  prep(first, end, src) fills the kernel's policy for a chunk and queues what readies its data — nothing for
+// the resident mesher; a mesh of ONE chunk prepares once, its data still stands in the write pass.  sc: the scene, with the
+// counters the scan may write (SCAN_MESH).  The mesh lands in e->meshTris / meshCount.
+template <class SRC, class PREP>
+int mesh_from_list(dsr_engine *e, const SceneP &sc, const int32_t *list, const int32_t *nPtr, int n, int2 *tileSums,
+                   unsigned long long cap, int chunk, PREP prep) {
+  MeshScratch scratch;
+  uint32_t *blockCount = nullptr, *blockOffset = nullptr;
+  int st;
+  if ((st = scratch.get(&blockCount, (size_t)n)) || (st = scratch.get(&blockOffset, (size_t)n))) return st;
+  MeshP mp; mp.voxelSize = e->s.voxel_size; mp.hashMask = (uint32_t)(e->noBuckets - 1); mp.noBuckets = e->noBuckets;
+  const int tiles = div_up(n, kTile);
+  const bool oneChunk = n <= chunk;
+  SRC src{};
+  for (int first = 0; first < n; first += chunk) {
+    const int end = (int)std::min<long long>((long long)first + chunk, n);
+    if ((st = prep(first, end, src))) return st;
+    LAUNCH(e, "mesh_count", (k_mesh_blocks<false, SRC>), dim3(std::min(8192, div_up(end - first, kMeshWaves))), dim3(64 * kMeshWaves),
+           sc, mp, list, nPtr, blockCount, (const uint32_t *)nullptr, (dsr_triangle *)nullptr, 0ull, src);
+  }
+  LAUNCH(e, "mesh_scan", k_u32_tile_sums, dim3(tiles), dim3(kTileThreads), (const uint32_t *)blockCount, nPtr, tileSums);
+  LAUNCH(e, "scan_tiles", k_scan_tile_sums, dim3(1), dim3(1024), tileSums, tiles, sc, (int)SCAN_MESH, 0);
+  LAUNCH(e, "mesh_scan", k_u32_tile_offsets, dim3(tiles), dim3(kTileThreads), (const uint32_t *)blockCount, nPtr,
+         (const int2 *)tileSums, blockOffset);
+  int total = 0;
+  HIP_TRY(hipMemcpyAsync(&total, sc.ctr + CTR_MESH_TOTAL, 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  if (total < 0) return fail(DSR_E_ARG, "mesh has more than 2^31 triangles");
+  const unsigned long long keep = std::min((unsigned long long)total, cap);
+  if (keep == 0) return DSR_OK;
+  if (hipMalloc(reinterpret_cast<void **>(&e->meshTris), (size_t)keep * sizeof(dsr_triangle)) != hipSuccess) {
+    e->meshTris = nullptr;
+    return fail(DSR_E_NOMEM, "mesh triangle buffer allocation failed");
+  }
+  for (int first = 0; first < n && st == DSR_OK; first += chunk) {
+    const int end = (int)std::min<long long>((long long)first + chunk, n);
+    if (!oneChunk && (st = prep(first, end, src))) break;
+    LAUNCH(e, "mesh_write", (k_mesh_blocks<true, SRC>), dim3(std::min(8192, div_up(end - first, kMeshWaves))), dim3(64 * kMeshWaves),
+           sc, mp, list, nPtr, blockCount, (const uint32_t *)blockOffset, e->meshTris, keep, src);
+  }
+  const hipError_t err = hipStreamSynchronize(e->stream);  // (also before the scratch goes)
+  if (st == DSR_OK && err != hipSuccess) st = fail(DSR_E_DEVICE, hipGetErrorString(err));
+  if (st == DSR_OK) e->meshCount = keep;
+  else { (void)hipFree(e->meshTris); e->meshTris = nullptr; }
+  return st;
+}
+int no_prep(int, int, MeshResident &) { return DSR_OK; }
+}  // namespace
+}  // extern "C++"
+
+int dsr_mesh_free(dsr_engine *e) {
+  CHECK_E(e);
+  return mesh_release(e);
+}
+
 // ITMMeshingEngine::MeshScene (an offline dump: host synchronisation is fine here)
 int dsr_mesh_scene(dsr_engine *e, uint64_t *n_triangles) {
   CHECK_E(e);
-  int st = dsr_mesh_free(e);
+  int st = mesh_release(e);
   if (st) return st;
   // ascending list of the allocated entries (shared with Decay(forceAllVoxels))
   LAUNCH(e, "mesh_candidates", k_allocated_count, dim3(e->numTilesE), dim3(kTileThreads), e->scene, e->E, e->tileSums);
@@ -1694,43 +1766,121 @@ int dsr_mesh_scene(dsr_engine *e, uint64_t *n_triangles) {
   HIP_TRY(hipStreamSynchronize(e->stream));
   if (n_triangles) *n_triangles = 0;
   if (n <= 0) return DSR_OK;
-  uint32_t *blockCount = nullptr, *blockOffset = nullptr;
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&blockCount), (size_t)n * 4));
-  if (hipMalloc(reinterpret_cast<void **>(&blockOffset), (size_t)n * 4) != hipSuccess) { (void)hipFree(blockCount); return fail(DSR_E_NOMEM, "mesh scratch allocation failed"); }
-  MeshP mp; mp.voxelSize = e->s.voxel_size; mp.hashMask = (uint32_t)(e->noBuckets - 1); mp.noBuckets = e->noBuckets;
-  const int grid = std::min(8192, div_up(n, kMeshWaves));
-  const int tiles = div_up(n, kTile);
-  LAUNCH(e, "mesh_count", (k_mesh_blocks<false>), dim3(grid), dim3(64 * kMeshWaves), e->scene, mp, (const int32_t *)e->decayCand, nPtr,
-         blockCount, (const uint32_t *)nullptr, (dsr_triangle *)nullptr, 0ull);
-  LAUNCH(e, "mesh_scan", k_u32_tile_sums, dim3(tiles), dim3(kTileThreads), (const uint32_t *)blockCount, nPtr, e->tileSums);
-  LAUNCH(e, "scan_tiles", k_scan_tile_sums, dim3(1), dim3(1024), e->tileSums, tiles, e->scene, (int)SCAN_MESH, 0);
-  LAUNCH(e, "mesh_scan", k_u32_tile_offsets, dim3(tiles), dim3(kTileThreads), (const uint32_t *)blockCount, nPtr,
-         (const int2 *)e->tileSums, blockOffset);
-  int total = 0;
-  hipError_t err = hipMemcpyAsync(&total, e->scene.ctr + CTR_MESH_TOTAL, 4, hipMemcpyDeviceToHost, e->stream);
-  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-  st = DSR_OK;
-  if (err != hipSuccess) st = fail(DSR_E_DEVICE, hipGetErrorString(err));
-  else if (total < 0) st = fail(DSR_E_ARG, "mesh has more than 2^31 triangles");
   // ITMMesh: noMaxTriangles = maxBlocks * 32; the append keeps the first noMaxTriangles - 1
   const unsigned long long cap = (unsigned long long)e->noBlocks * 32ull - 1ull;
-  const unsigned long long keep = std::min((unsigned long long)std::max(total, 0), cap);
-  if (st == DSR_OK && keep > 0) {
-    if (hipMalloc(reinterpret_cast<void **>(&e->meshTris), (size_t)keep * sizeof(dsr_triangle)) != hipSuccess) {
-      e->meshTris = nullptr;
-      st = fail(DSR_E_NOMEM, "mesh triangle buffer allocation failed");
-    } else {
-      LAUNCH(e, "mesh_write", (k_mesh_blocks<true>), dim3(grid), dim3(64 * kMeshWaves), e->scene, mp, (const int32_t *)e->decayCand,
-             nPtr, blockCount, (const uint32_t *)blockOffset, e->meshTris, keep);
-      err = hipStreamSynchronize(e->stream);
-      if (err != hipSuccess) st = fail(DSR_E_DEVICE, hipGetErrorString(err));
-      else e->meshCount = keep;
-    }
-  }
-  (void)hipStreamSynchronize(e->stream);
-  (void)hipFree(blockCount); (void)hipFree(blockOffset);
+  st = mesh_from_list<MeshResident>(e, e->scene, e->decayCand, nPtr, n, e->tileSums, cap, n, no_prep);
   if (st == DSR_OK && n_triangles) *n_triangles = e->meshCount;
   return st;
+}
+
+// ---- the complete mesh of a swapping engine (include/dsr_mesh.h, k_mesh_complete.h; builder-defined)
+
+int32_t dsr_mesh_abi_version(void) { return DSR_MESH_ABI_VERSION; }
+
+namespace {
+long long host_store_slots(const dsr_engine *e) { return (long long)e->hostSlabs.size() * e->scene.slabBlocks; }
+}  // namespace
+
+int dsr_mesh_scene_complete(dsr_engine *e, uint64_t *n_triangles) {
+  // (no deferred render is queued here: it reads the scene, as this call does, and stays pending)
+  CHECK_E_NOFLUSH(e);
+  int st = mesh_release(e);
+  if (st) return st;
+  if (n_triangles) *n_triangles = 0;
+  // Everything this call writes is its own: the list, the tile sums and — through a copy of the scene's parameters — the
+  // counters the scans leave their totals in.  The engine's scratch and counters keep what the last frame left.
+  MeshScratch scratch;
+  SceneP sc = e->scene;
+  int2 *tileSums = nullptr;
+  int32_t *list = nullptr;
+  if ((st = scratch.get(&sc.ctr, (size_t)CTR_COUNT)) || (st = scratch.get(&tileSums, (size_t)e->numTilesE)) ||
+      (st = scratch.get(&list, (size_t)e->E)))
+    return st;
+  HIP_TRY(hipMemsetAsync(sc.ctr, 0, CTR_COUNT * 4, e->stream));
+  LAUNCH(e, "mesh_candidates", k_owning_count, dim3(e->numTilesE), dim3(kTileThreads), sc, e->E, tileSums);
+  LAUNCH(e, "scan_tiles", k_scan_tile_sums, dim3(1), dim3(1024), tileSums, e->numTilesE, sc, (int)SCAN_NCAND, e->E);
+  LAUNCH(e, "mesh_candidates", k_owning_write, dim3(e->numTilesE), dim3(kTileThreads), sc, e->E, (const int2 *)tileSums, list, e->E);
+  const int32_t *nPtr = sc.ctr + CTR_DECAY_NCAND;
+  int32_t head[2] = {0, 0};  // list length; host slots handed out (an upper bound of the stored entries)
+  HIP_TRY(hipMemcpyAsync(&head[0], nPtr, 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(&head[1], e->scene.ctr + CTR_HOST_USED, 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const int n = head[0];
+  if (n <= 0) return DSR_OK;
+  const unsigned long long cap = (unsigned long long)std::max(e->noBlocks, n) * 32ull - 1ull;
+  if (!e->scene.swapStored) {  // nothing is ever stored: the resident mesher over the same list
+    st = mesh_from_list<MeshResident>(e, sc, list, nPtr, n, tileSums, cap, n, no_prep);
+  } else {
+    if (head[1] < 0 || head[1] > host_store_slots(e)) return fail(DSR_E_DEVICE, "host store inconsistent");
+    // The pool: a chunk of the list reaches at most 8 entries per listed one, and never more than the store holds.  A chunk of
+    // 2^17 entries bounds it at 1 GiB; a map with fewer stored entries than that takes ONE chunk whatever its size, and only a
+    // mesh of several chunks fetches planes twice (count pass, write pass).  env DSR_MESH_CHUNK: the chunk (tests).
+    int chunk = 1 << 17;
+    if (const char *c = getenv("DSR_MESH_CHUNK")) chunk = std::max(1, atoi(c));
+    if (head[1] <= 8ll * chunk) chunk = std::max(chunk, n);
+    const int poolCap = (int)std::min<long long>(head[1], 8ll * std::min(chunk, n));
+    int32_t *planeOf = nullptr, *poolIds = nullptr, *poolCtr = nullptr;
+    uint8_t *pool = nullptr;
+    if ((st = scratch.get(&planeOf, (size_t)e->E)) || (st = scratch.get(&poolIds, (size_t)poolCap)) ||
+        (st = scratch.get(&poolCtr, 2)) || (st = scratch.get(&pool, (size_t)poolCap * kPlaneBytes)))
+      return st;
+    MeshP mp; mp.voxelSize = e->s.voxel_size; mp.hashMask = (uint32_t)(e->noBuckets - 1); mp.noBuckets = e->noBuckets;
+    const int noSlots = (int)std::min<long long>(host_store_slots(e), 0x7fffffff);
+    HIP_TRY(hipMemsetAsync(poolCtr, 0, 8, e->stream));  // (the overflow flag, poolCtr[1], is sticky over the chunks)
+    auto prep = [&](int first, int end, MeshPooled &src) -> int {
+      src.planeOf = planeOf; src.pool = pool; src.firstItem = first; src.endItem = end;
+      HIP_TRY(hipMemsetAsync(planeOf, 0xff, (size_t)e->E * 4, e->stream));
+      HIP_TRY(hipMemsetAsync(poolCtr, 0, 4, e->stream));
+      LAUNCH(e, "mesh_mark", k_mesh_mark, dim3(div_up((long long)(end - first) * 8, 256)), dim3(256), sc, mp, (const int32_t *)list,
+             nPtr, first, end, planeOf, poolIds, poolCap, poolCtr);
+      LAUNCH(e, "mesh_gather", k_mesh_gather, dim3(std::max(1, std::min(1024, div_up(poolCap, 4)))), dim3(256), sc, (int)e->s.max_w,
+             e->noBlocks, noSlots, (const int32_t *)poolIds, (const int32_t *)poolCtr, poolCap, pool);
+      return DSR_OK;
+    };
+    st = mesh_from_list<MeshPooled>(e, sc, list, nPtr, n, tileSums, cap, chunk, prep);
+    if (st == DSR_OK) {
+      int32_t over = 0;
+      HIP_TRY(hipMemcpy(&over, poolCtr + 1, 4, hipMemcpyDeviceToHost));
+      if (over) { (void)mesh_release(e); return fail(DSR_E_DEVICE, "mesh plane pool overflow"); }
+    }
+  }
+  if (st == DSR_OK && n_triangles) *n_triangles = e->meshCount;
+  return st;
+}
+
+int dsr_save_scene_to_mesh_complete(dsr_engine *e, const char *path) {
+  int st = dsr_mesh_scene_complete(e, nullptr);
+  if (st == DSR_OK) st = dsr_mesh_write_obj(e, path);
+  if (e) (void)mesh_release(e);
+  return st;
+}
+
+int dsr_dump_merged_block(dsr_engine *e, int entry, dsr_voxel *out, int *present) {
+  CHECK_E_NOFLUSH(e);
+  if (!present || entry < 0 || entry >= e->E) return fail(DSR_E_ARG, "bad entry");
+  *present = 0;
+  MeshScratch scratch;
+  uint8_t *blk = nullptr;
+  int32_t *flag = nullptr;
+  int st;
+  if ((st = scratch.get(&blk, (size_t)kBlockBytes)) || (st = scratch.get(&flag, 1))) return st;
+  const int noSlots = (int)std::min<long long>(host_store_slots(e), 0x7fffffff);
+  LAUNCH(e, "merged_block", k_merged_block, dim3(1), dim3(64), e->scene, (int)e->s.max_w, e->noBlocks, noSlots, entry, blk, flag);
+  std::vector<uint8_t> b(kBlockBytes);
+  int32_t f = 0;
+  HIP_TRY(hipMemcpyAsync(&f, flag, 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(b.data(), blk, kBlockBytes, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  if (!f) return DSR_OK;
+  *present = 1;
+  for (int v = 0; out && v < kBlockSize3; ++v) {
+    dsr_voxel o; memset(&o, 0, sizeof o);
+    memcpy(&o.sdf, b.data() + kOffSdf + v * 2, 2);
+    o.w_depth = b[kOffWDepth + v]; o.w_color = b[kOffClr + v * 4 + 3];
+    o.clr[0] = b[kOffClr + v * 4]; o.clr[1] = b[kOffClr + v * 4 + 1]; o.clr[2] = b[kOffClr + v * 4 + 2];
+    out[v] = o;
+  }
+  return DSR_OK;
 }
 
 int dsr_mesh_get(dsr_engine *e, dsr_triangle *out, uint64_t first, uint64_t count) {

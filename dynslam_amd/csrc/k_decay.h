@@ -225,29 +225,32 @@ __global__ __launch_bounds__(kTileThreads) void k_decay_commit(SceneP s, const i
     }
 }
 
-// forceAllVoxels: candidates = every entry with ptr >= 0, ascending (ordered compaction)
-__global__ __launch_bounds__(kTileThreads) void k_allocated_count(SceneP s, int noTotalEntries,
-                                                                  int2 *__restrict__ tileSums) {
-  __shared__ int2 lds[kTileThreads / 64];
+// forceAllVoxels: candidates = every entry with ptr >= 0, ascending (ordered compaction).  STORED (k_mesh_complete.h): every entry
+// that owns voxel DATA — resident, or swapped out with a copy in the host store
+template <bool STORED>
+__device__ __forceinline__ bool entry_listed(const SceneP &s, int t) {
+  return s.table[t].ptr >= 0 || (STORED && s.swapStored && s.swapStored[t] != 0);
+}
+template <bool STORED>
+__device__ __forceinline__ void allocated_count_body(const SceneP &s, int noTotalEntries, int2 *__restrict__ tileSums, int2 *lds) {
   const int base = blockIdx.x * kTile + threadIdx.x * kTileItems;
   int2 c = make_int2(0, 0);
 #pragma unroll
   for (int j = 0; j < kTileItems; ++j)
-    if (base + j < noTotalEntries && s.table[base + j].ptr >= 0) c.x++;
+    if (base + j < noTotalEntries && entry_listed<STORED>(s, base + j)) c.x++;
   int2 total;
   wg_exclusive_scan2<kTileThreads>(c, total, lds);
   if (threadIdx.x == 0) tileSums[blockIdx.x] = total;
 }
-__global__ __launch_bounds__(kTileThreads) void k_allocated_write(SceneP s, int noTotalEntries,
-                                                                  const int2 *__restrict__ tileOffsets,
-                                                                  int32_t *__restrict__ out, int capacity) {
-  __shared__ int2 lds[kTileThreads / 64];
+template <bool STORED>
+__device__ __forceinline__ void allocated_write_body(const SceneP &s, int noTotalEntries, const int2 *__restrict__ tileOffsets,
+                                                     int32_t *__restrict__ out, int capacity, int2 *lds) {
   const int base = blockIdx.x * kTile + threadIdx.x * kTileItems;
   bool a[kTileItems];
   int2 c = make_int2(0, 0);
 #pragma unroll
   for (int j = 0; j < kTileItems; ++j) {
-    a[j] = base + j < noTotalEntries && s.table[base + j].ptr >= 0;
+    a[j] = base + j < noTotalEntries && entry_listed<STORED>(s, base + j);
     if (a[j]) c.x++;
   }
   int2 total;
@@ -257,6 +260,17 @@ __global__ __launch_bounds__(kTileThreads) void k_allocated_write(SceneP s, int 
 #pragma unroll
   for (int j = 0; j < kTileItems; ++j)
     if (a[j]) { if (rank < capacity) out[rank] = base + j; rank++; }
+}
+__global__ __launch_bounds__(kTileThreads) void k_allocated_count(SceneP s, int noTotalEntries,
+                                                                  int2 *__restrict__ tileSums) {
+  __shared__ int2 lds[kTileThreads / 64];
+  allocated_count_body<false>(s, noTotalEntries, tileSums, lds);
+}
+__global__ __launch_bounds__(kTileThreads) void k_allocated_write(SceneP s, int noTotalEntries,
+                                                                  const int2 *__restrict__ tileOffsets,
+                                                                  int32_t *__restrict__ out, int capacity) {
+  __shared__ int2 lds[kTileThreads / 64];
+  allocated_write_body<false>(s, noTotalEntries, tileOffsets, out, capacity, lds);
 }
 
 // ITMVisualisationEngine::FindVisibleBlocks for a free camera, DENSE: a thread per ALLOCATED entry

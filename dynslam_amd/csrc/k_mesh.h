@@ -4,12 +4,12 @@
 // runs one 8x8x8 thread block per hash entry and appends triangles with atomicAdd (arbitrary
 // order); here the output order is the serial engine's (entries ascending, voxels z/y/x,
 // triangles in table order) so that the mesh is reproducible and comparable bit for bit:
-//   pass 1  k_mesh_blocks<false>: a wave64 per allocated block (list built by k_allocated_*) stages
+//   pass 1  k_mesh_blocks<false, SRC>: a wave64 per allocated block (list built by k_allocated_*) stages
 //           the 9x9x9 corner lattice of the block — its own sdf plane plus the first layer of the 7
 //           neighbours in +x/+y/+z, found with 8 table lookups done by 8 lanes — in LDS, classifies
 //           the 512 cells and counts the triangles of the block;
 //   scan    block counts -> block offsets (tile sums + one-workgroup scan + tile pass);
-//   pass 2  k_mesh_blocks<true>: same staging, a wave prefix over the lanes' counts gives every cell
+//   pass 2  k_mesh_blocks<true, SRC>: same staging, a wave prefix over the lanes' counts gives every cell
 //           its slot; vertices by sdfInterp on the cell edges, scaled to metres.
 // Arithmetic follows ITMMeshingEngine.h (findPointNeighbors, sdfInterp, buildVertList).
 #pragma once
@@ -38,19 +38,34 @@ __device__ __forceinline__ float3 sdf_interp(float3 p1, float3 p2, float v1, flo
   return make_float3(p1.x + t * (p2.x - p1.x), p1.y + t * (p2.y - p1.y), p1.z + t * (p2.z - p1.z));
 }
 
-template <bool WRITE>
+// WHERE THE SDF PLANE OF A BLOCK LIES is a policy of the kernel.  A policy answers, for a table entry whose position matches:
+// does it own voxel data (owns), and under which code (locate) (an int the wave keeps in LDS; -1 = none); for a code: the plane's address; and
+// which part of the list this launch covers.  MeshResident is dsr_mesh_scene's: the entries with ptr >= 0, code = ptr, the plane
+// inside the block array.  k_mesh_complete.h has the one that also knows the host store.
+struct MeshResident {
+  __device__ __forceinline__ int first() const { return 0; }
+  __device__ __forceinline__ int end(int n) const { return n; }
+  __device__ __forceinline__ bool owns(const SceneP &, uint32_t, int ptr) const { return ptr >= 0; }
+  __device__ __forceinline__ int locate(uint32_t, int ptr) const { return ptr; }
+  __device__ __forceinline__ bool has(int code) const { return code >= 0; }
+  __device__ __forceinline__ const uint8_t *sdf_plane(const SceneP &s, int code) const {
+    return s.vba + (size_t)code * kBlockBytes + kOffSdf;
+  }
+};
+
+template <bool WRITE, class SRC = MeshResident>
 __global__ __launch_bounds__(64 * kMeshWaves) void k_mesh_blocks(SceneP s, MeshP mp, const int32_t *__restrict__ blockList,
                                                                  const int32_t *__restrict__ nPtr,
                                                                  uint32_t *__restrict__ blockCount,
                                                                  const uint32_t *__restrict__ blockOffset,
-                                                                 dsr_triangle *__restrict__ out, unsigned long long cap) {
+                                                                 dsr_triangle *__restrict__ out, unsigned long long cap, SRC src) {
   __shared__ int s_lat[kMeshWaves][9 * 9 * 9];
   __shared__ int s_nbr[kMeshWaves][8];
-  const int n = *nPtr;
+  const int n = src.end(*nPtr);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int *lat = s_lat[wave];
   int *nbr = s_nbr[wave];
-  for (int i = blockIdx.x * kMeshWaves + wave; i < n; i += gridDim.x * kMeshWaves) {
+  for (int i = src.first() + blockIdx.x * kMeshWaves + wave; i < n; i += gridDim.x * kMeshWaves) {
     const dsr_hash_entry he = load_entry(s.table, (uint32_t)blockList[i]);
     // ---- the 8 blocks the lattice touches: lane k looks up block pos + (k&1, k>>1&1, k>>2)
     if (lane < 8) {
@@ -59,7 +74,7 @@ __global__ __launch_bounds__(64 * kMeshWaves) void k_mesh_blocks(SceneP s, MeshP
       uint32_t h = hash_index(bx, by, bz, mp.hashMask);
       while (true) {  // ITMRepresentationAccess.h findVoxel
         const dsr_hash_entry q = load_entry(s.table, h);
-        if (q.pos[0] == bx && q.pos[1] == by && q.pos[2] == bz && q.ptr >= 0) { ptr = q.ptr; break; }
+        if (q.pos[0] == bx && q.pos[1] == by && q.pos[2] == bz && src.owns(s, h, q.ptr)) { ptr = src.locate(h, q.ptr); break; }
         if (q.offset < 1) break;
         h = (uint32_t)(mp.noBuckets + q.offset - 1);
       }
@@ -72,9 +87,9 @@ __global__ __launch_bounds__(64 * kMeshWaves) void k_mesh_blocks(SceneP s, MeshP
       const int cx = c % 9, cy = (c / 9) % 9, cz = c / 81;
       const int ptr = nbr[(cx >> 3) | ((cy >> 3) << 1) | ((cz >> 3) << 2)];
       int v = kMissingCorner;
-      if (ptr >= 0) {
+      if (src.has(ptr)) {
         const int lin = (cx & 7) + ((cy & 7) << 3) + ((cz & 7) << 6);
-        v = (int)*reinterpret_cast<const short *>(s.vba + (size_t)ptr * kBlockBytes + kOffSdf + lin * 2);
+        v = (int)*reinterpret_cast<const short *>(src.sdf_plane(s, ptr) + lin * 2);
       }
       lat[c] = v;
     }

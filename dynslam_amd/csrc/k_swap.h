@@ -114,8 +114,54 @@ __global__ __launch_bounds__(256) void k_swapin_fetch(SceneP s, const int32_t *_
   }
 }
 
-// ITMSwappingEngine.h combineVoxelDepthInformation / combineVoxelColorInformation on the plane-wise
-// layout.  One wave per transferred block, lane = 8 voxels.
+// ITMSwappingEngine.h combineVoxelDepthInformation on one voxel: (sdf, w) of the local block <- its merge with the stored copy's
+// (oldSdf, oldW).  Shared with the complete mesher (k_mesh_complete.h), which needs the sdf the next swap-in WOULD leave.
+__device__ __forceinline__ void combine_voxel_depth(short oldSdf, int oldW, int maxW, short &sdf, int &w) {
+  if (oldW == 0) return;
+  float newF = sdf_to_float((float)sdf);
+  const float oldF = sdf_to_float((float)oldSdf);
+  newF = (float)oldW * oldF + (float)w * newF;
+  w = oldW + w;
+  newF /= (float)w;
+  w = w < maxW ? w : maxW;
+  sdf = sdf_from_float(newF);
+}
+// ... combineVoxelColorInformation, on the (r, g, b, w_color) word
+__device__ __forceinline__ uchar4 combine_voxel_colour(uchar4 sc, uchar4 dc, int maxW) {
+  int newW = dc.w;
+  const int oldW = sc.w;
+  if (oldW == 0) return dc;
+  float nx = (float)dc.x / 255.0f, ny = (float)dc.y / 255.0f, nz = (float)dc.z / 255.0f;
+  const float ox = (float)sc.x / 255.0f, oy = (float)sc.y / 255.0f, oz = (float)sc.z / 255.0f;
+  nx = ox * (float)oldW + nx * (float)newW;
+  ny = oy * (float)oldW + ny * (float)newW;
+  nz = oz * (float)oldW + nz * (float)newW;
+  newW = oldW + newW;
+  nx /= (float)newW; ny /= (float)newW; nz /= (float)newW;
+  newW = newW < maxW ? newW : maxW;
+  return make_uchar4((uint8_t)f2i(nx * 255.0f), (uint8_t)f2i(ny * 255.0f), (uint8_t)f2i(nz * 255.0f), (uint8_t)newW);
+}
+// src (the stored copy) merged into dst, both plane-wise blocks; this lane's 8 voxels
+__device__ __forceinline__ void combine_block_lane(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, int lane, int maxW) {
+#pragma unroll 1
+  for (int x = 0; x < 8; ++x) {
+    const int v = lane * 8 + x;
+    const int oldW = src[kOffWDepth + v];
+    if (oldW != 0) {  // depth
+      short sdf = *reinterpret_cast<const short *>(dst + kOffSdf + v * 2);
+      int w = dst[kOffWDepth + v];
+      combine_voxel_depth(*reinterpret_cast<const short *>(src + kOffSdf + v * 2), oldW, maxW, sdf, w);
+      dst[kOffWDepth + v] = (uint8_t)w;
+      *reinterpret_cast<short *>(dst + kOffSdf + v * 2) = sdf;
+    }
+    const uchar4 sc = *reinterpret_cast<const uchar4 *>(src + kOffClr + v * 4);  // (r, g, b, w_color)
+    if (sc.w != 0)
+      *reinterpret_cast<uchar4 *>(dst + kOffClr + v * 4) =
+          combine_voxel_colour(sc, *reinterpret_cast<const uchar4 *>(dst + kOffClr + v * 4), maxW);
+  }
+}
+
+// One wave per transferred block, lane = 8 voxels.
 __global__ __launch_bounds__(256) void k_swapin_combine(SceneP s, int maxW, const int32_t *__restrict__ ids,
                                                         const uint8_t *__restrict__ storedFlags,
                                                         const uint8_t *__restrict__ staging) {
@@ -127,46 +173,7 @@ __global__ __launch_bounds__(256) void k_swapin_combine(SceneP s, int maxW, cons
     const int ptr = s.table[id].ptr;
     const bool stored = storedFlags[i] != 0;
     if (stored && ptr < 0) continue;  // no block could be given to it: stays in state 1
-    if (stored) {
-      const uint8_t *src = staging + (size_t)i * kBlockBytes;
-      uint8_t *dst = s.vba + (size_t)ptr * kBlockBytes;
-#pragma unroll 1
-      for (int x = 0; x < 8; ++x) {
-        const int v = lane * 8 + x;
-        {  // depth
-          int newW = dst[kOffWDepth + v];
-          const int oldW = src[kOffWDepth + v];
-          if (oldW != 0) {
-            float newF = sdf_to_float((float)*reinterpret_cast<const short *>(dst + kOffSdf + v * 2));
-            const float oldF = sdf_to_float((float)*reinterpret_cast<const short *>(src + kOffSdf + v * 2));
-            newF = (float)oldW * oldF + (float)newW * newF;
-            newW = oldW + newW;
-            newF /= (float)newW;
-            newW = newW < maxW ? newW : maxW;
-            dst[kOffWDepth + v] = (uint8_t)newW;
-            *reinterpret_cast<short *>(dst + kOffSdf + v * 2) = sdf_from_float(newF);
-          }
-        }
-        {  // colour
-          const uchar4 dc = *reinterpret_cast<const uchar4 *>(dst + kOffClr + v * 4);  // (r, g, b, w_color)
-          const uchar4 sc = *reinterpret_cast<const uchar4 *>(src + kOffClr + v * 4);
-          int newW = dc.w;
-          const int oldW = sc.w;
-          if (oldW != 0) {
-            float nx = (float)dc.x / 255.0f, ny = (float)dc.y / 255.0f, nz = (float)dc.z / 255.0f;
-            const float ox = (float)sc.x / 255.0f, oy = (float)sc.y / 255.0f, oz = (float)sc.z / 255.0f;
-            nx = ox * (float)oldW + nx * (float)newW;
-            ny = oy * (float)oldW + ny * (float)newW;
-            nz = oz * (float)oldW + nz * (float)newW;
-            newW = oldW + newW;
-            nx /= (float)newW; ny /= (float)newW; nz /= (float)newW;
-            newW = newW < maxW ? newW : maxW;
-            *reinterpret_cast<uchar4 *>(dst + kOffClr + v * 4) =
-                make_uchar4((uint8_t)f2i(nx * 255.0f), (uint8_t)f2i(ny * 255.0f), (uint8_t)f2i(nz * 255.0f), (uint8_t)newW);
-          }
-        }
-      }
-    }
+    if (stored) combine_block_lane(staging + (size_t)i * kBlockBytes, s.vba + (size_t)ptr * kBlockBytes, lane, maxW);
     if (lane == 0) s.swapState[id] = 2;
   }
 }

@@ -705,6 +705,34 @@ class EngineCore:
     def save_scene_to_mesh(self, path):
         self._check(self.api.save_scene_to_mesh(self._h, str(path).encode()))
 
+    # ---- the complete mesh of a swapping engine (include/dsr_mesh.h; builder-defined)
+    def _mesh_api(self):
+        if not hasattr(self, "_mapi"):
+            self._mapi = _capi.bind_mesh(self.api.lib, self.api.prefix)
+        if self._mapi is None:
+            raise DsrError(_capi.DSR_E_ARG, f"this backend ({self.api.prefix}*) has no include/dsr_mesh.h entry points")
+        return self._mapi
+
+    def mesh_scene_complete(self):
+        """mesh_scene over every entry that owns voxel data, the blocks in the host store included (dsr_mesh_scene_complete);
+        reads only.  Returns the triangles as float32 [n, 3, 3] (metres); mesh_write_obj / mesh_free serve the result."""
+        n = C.c_uint64(0)
+        self._check(self._mesh_api().mesh_scene_complete(self._h, C.byref(n)))
+        out = np.empty((n.value, 3, 3), np.float32)
+        if n.value:
+            self._check(self.api.mesh_get(self._h, out.ctypes.data_as(C.c_void_p), 0, n.value))
+        return out
+
+    def save_scene_to_mesh_complete(self, path):
+        self._check(self._mesh_api().save_scene_to_mesh_complete(self._h, str(path).encode()))
+
+    def dump_merged_block(self, entry):
+        """For tests: the block of a table entry as the complete mesher sees it (dsr_dump_merged_block), None if it owns no data."""
+        out = np.empty(BLOCK_SIZE3, VOXEL_DTYPE)
+        present = C.c_int(0)
+        self._check(self._mesh_api().dump_merged_block(self._h, int(entry), _ptr(out), C.byref(present)))
+        return out if present.value else None
+
     def profile_reset(self):
         self._check(self.api.profile_reset(self._h))
 
@@ -910,10 +938,14 @@ class InfiniTamDriver:
     def Reset(self):
         self.core.reset_scene()
 
-    def SaveSceneToMesh(self, path):
+    def SaveSceneToMesh(self, path, complete=False):
         """ITMMainEngine::SaveSceneToMesh as called by DynSlam::SaveStaticMap (DynSlam.cpp:188-196)
-        and, per instance, InstanceReconstructor::SaveObjectToMesh (InstanceReconstructor.cpp:736-763)."""
-        self.core.save_scene_to_mesh(path)
+        and, per instance, InstanceReconstructor::SaveObjectToMesh (InstanceReconstructor.cpp:736-763).
+        complete=True (builder-defined, include/dsr_mesh.h): the whole map of a swapping engine, host-store blocks included."""
+        if complete:
+            self.core.save_scene_to_mesh_complete(path)
+        else:
+            self.core.save_scene_to_mesh(path)
 
     def SaveToFile(self, path):
         """ITMMainEngine::SaveToFile of InfiniTAM v3 (builder-defined here: the reference's fork has no checkpoint): the volume's

@@ -26,6 +26,7 @@
 #include "../include/dsr.h"
 #include "../include/dsr_track.h"
 #include "../include/dsr_snapshot.h"
+#include "../include/dsr_mesh.h"
 
 // The tracker's entry points are referenced WEAKLY: a host linked against a library without them (the CPU oracle's orc_* build
 // of the reference's hosts) still links, and ITMTrackingController::Track then throws as it did before the tracker existed.
@@ -35,6 +36,9 @@ void dsr_track_default_settings(dsr_track_settings *out) __attribute__((weak));
 // ... and so are the snapshot's (include/dsr_snapshot.h): SaveToFile / LoadFromFile throw on a library without them
 int dsr_snapshot_save(dsr_engine *e, const char *path) __attribute__((weak));
 int dsr_snapshot_load(dsr_engine *e, const char *path) __attribute__((weak));
+// ... and the complete mesher's (include/dsr_mesh.h): SaveCompleteSceneToMesh / MeshSceneComplete throw on a library without them
+int dsr_mesh_scene_complete(dsr_engine *e, uint64_t *n_triangles) __attribute__((weak));
+int dsr_save_scene_to_mesh_complete(dsr_engine *e, const char *path) __attribute__((weak));
 }
 
 #ifndef SDF_BLOCK_SIZE
@@ -434,6 +438,13 @@ template <class TVoxel, class TIndex> class ITMMeshingEngine {
     ITMLib::Engine::dsr_throw(dsr_mesh_scene(scene->e, &n));
     mesh->bind(scene->e, n);
   }
+  // BUILDER-DEFINED (include/dsr_mesh.h): MeshScene over every block of the map, the ones swapped out to the host included
+  virtual void MeshSceneComplete(ITMMesh *mesh, const ITMScene<TVoxel, TIndex> *scene) {
+    if (!dsr_mesh_scene_complete) throw std::runtime_error("this library has no complete mesher (include/dsr_mesh.h)");
+    uint64_t n = 0;
+    ITMLib::Engine::dsr_throw(dsr_mesh_scene_complete(scene->e, &n));
+    mesh->bind(scene->e, n);
+  }
 };
 template <class TVoxel, class TIndex> class ITMMeshingEngine_CUDA : public ITMMeshingEngine<TVoxel, TIndex> {
  public:
@@ -599,6 +610,12 @@ class ITMMainEngine {
   }
   // ITMMainEngine::SaveSceneToMesh (DynSlam.cpp:188-196)
   void SaveSceneToMesh(const char *objFileName) { ITMLib::Engine::dsr_throw(dsr_save_scene_to_mesh(engine_, objFileName)); }
+  // BUILDER-DEFINED (include/dsr_mesh.h; upstream has the same gap): the mesh of the WHOLE map — with swapping on, SaveSceneToMesh
+  // writes the resident blocks only.  The one-line change in DynSlam::SaveStaticMap: INTEGRATION.md.
+  void SaveCompleteSceneToMesh(const char *objFileName) {
+    if (!dsr_save_scene_to_mesh_complete) throw std::runtime_error("this library has no complete mesher (include/dsr_mesh.h)");
+    ITMLib::Engine::dsr_throw(dsr_save_scene_to_mesh_complete(engine_, objFileName));
+  }
   // ITMMainEngine::SaveToFile / LoadFromFile: the names of InfiniTAM v3, BUILDER-DEFINED here (the reference's fork of v2 has no
   // checkpoint).  The volume's complete state — scene, render states, tracking maps, view, pose — as a snapshot file
   // (include/dsr_snapshot.h); the loading engine was built with equal settings.  After LoadFromFile the engine's pose is the saved
