@@ -429,13 +429,19 @@ def bind_snapshot(lib, prefix):
 
 
 # ---- include/dsr_mesh.h: the complete mesh of a swapping engine.  A table of its own, like the snapshot's (the oracle has none).
-MESH_ABI_VERSION = 1  # == DSR_MESH_ABI_VERSION
+MESH_ABI_VERSION = 2  # == DSR_MESH_ABI_VERSION
 
 MESH_SIGNATURES = {
     "mesh_abi_version": (C.c_int32, []),
     "mesh_scene_complete": (C.c_int, [_H, C.POINTER(C.c_uint64)]),
     "save_scene_to_mesh_complete": (C.c_int, [_H, C.c_char_p]),
     "dump_merged_block": (C.c_int, [_H, C.c_int, _P, C.POINTER(C.c_int)]),
+    # coloured meshes (version 2)
+    "mesh_scene_coloured": (C.c_int, [_H, C.c_int, C.POINTER(C.c_uint64)]),
+    "mesh_get_colours": (C.c_int, [_H, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "mesh_write_obj_coloured": (C.c_int, [_H, C.c_char_p]),
+    "mesh_write_ply": (C.c_int, [_H, C.c_char_p]),
+    "save_scene_to_mesh_coloured": (C.c_int, [_H, C.c_char_p, C.c_int]),
 }
 
 

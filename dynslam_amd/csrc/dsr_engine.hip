@@ -163,7 +163,7 @@ void free_all(dsr_engine *e) {
     F(rs->visibleIDs); F(rs->visibleIDsAlt); F(rs->visBlocks); F(rs->visBlocksAlt); F(rs->visType); F(rs->minmax); F(rs->raycastResult); F(rs->raycastImage); F(rs->rayBox);
   }
   dsr_internal::tracker_free(e);
-  F(e->tileSums); F(e->integrateStats); F(e->allocList); F(e->allocWork); F(e->meshTris); F(e->rgb); F(e->depth); F(e->depthTmp); F(e->rawDepth); F(e->pointsMap); F(e->normalsMap);
+  F(e->tileSums); F(e->integrateStats); F(e->allocList); F(e->allocWork); F(e->meshTris); F(e->meshClr); F(e->rgb); F(e->depth); F(e->depthTmp); F(e->rawDepth); F(e->pointsMap); F(e->normalsMap);
   F(e->freeDepth); F(e->aosScratch);
   F(e->fifoPlanes); F(e->decayCand); F(e->decayFlags);
   if (e->maskHost) (void)hipHostFree(e->maskHost);
@@ -1676,8 +1676,11 @@ int dsr_dump_stored_block(dsr_engine *e, int entry, dsr_voxel *out, int *present
 extern "C++" {  // (templates: this part of the file sits inside the extern "C" block of the ABI)
 namespace {
 int mesh_release(dsr_engine *e) {
-  if (e->meshTris) { HIP_TRY(hipStreamSynchronize(e->stream)); (void)hipFree(e->meshTris); e->meshTris = nullptr; }
+  if (e->meshTris || e->meshClr) HIP_TRY(hipStreamSynchronize(e->stream));
+  if (e->meshTris) { (void)hipFree(e->meshTris); e->meshTris = nullptr; }
+  if (e->meshClr) { (void)hipFree(e->meshClr); e->meshClr = nullptr; }
   e->meshCount = 0;
+  e->meshColoured = false;
   return DSR_OK;
 }
 
@@ -1697,8 +1700,9 @@ struct MeshScratch {
 // Marching cubes over the ordered list of n entries (its length on the device: *nPtr), in chunks of `chunk` entries: count per
 // block, scan, write.  prep(first, end, src) fills the kernel's policy for a chunk and queues what readies its data — nothing for
 // the resident mesher; a mesh of ONE chunk prepares once, its data still stands in the write pass.  sc: the scene, with the
-// counters the scan may write (SCAN_MESH).  The mesh lands in e->meshTris / meshCount.
-template <class SRC, class PREP>
+// counters the scan may write (SCAN_MESH).  The mesh lands in e->meshTris / meshCount; COLOUR: the write pass is the coloured one
+// (MeshColoured<SRC>; SRC has clr_plane) and the vertex colours land in e->meshClr.
+template <class SRC, bool COLOUR = false, class PREP>
 int mesh_from_list(dsr_engine *e, const SceneP &sc, const int32_t *list, const int32_t *nPtr, int n, int2 *tileSums,
                    unsigned long long cap, int chunk, PREP prep) {
   MeshScratch scratch;
@@ -1729,19 +1733,38 @@ int mesh_from_list(dsr_engine *e, const SceneP &sc, const int32_t *list, const i
     e->meshTris = nullptr;
     return fail(DSR_E_NOMEM, "mesh triangle buffer allocation failed");
   }
+  if (COLOUR && hipMalloc(reinterpret_cast<void **>(&e->meshClr), (size_t)keep * sizeof(dsr_triangle_colour)) != hipSuccess) {
+    (void)hipFree(e->meshTris); e->meshTris = nullptr; e->meshClr = nullptr;
+    return fail(DSR_E_NOMEM, "mesh colour buffer allocation failed");
+  }
   for (int first = 0; first < n && st == DSR_OK; first += chunk) {
     const int end = (int)std::min<long long>((long long)first + chunk, n);
     if (!oneChunk && (st = prep(first, end, src))) break;
-    LAUNCH(e, "mesh_write", (k_mesh_blocks<true, SRC>), dim3(std::min(8192, div_up(end - first, kMeshWaves))), dim3(64 * kMeshWaves),
-           sc, mp, list, nPtr, blockCount, (const uint32_t *)blockOffset, e->meshTris, keep, src);
+    if constexpr (COLOUR) {
+      MeshColoured<SRC> csrc;
+      static_cast<SRC &>(csrc) = src;
+      csrc.colours = e->meshClr;
+      LAUNCH(e, "mesh_write_colour", (k_mesh_blocks<true, MeshColoured<SRC>>), dim3(std::min(8192, div_up(end - first, kMeshWaves))),
+             dim3(64 * kMeshWaves), sc, mp, list, nPtr, blockCount, (const uint32_t *)blockOffset, e->meshTris, keep, csrc);
+    }
+    else {
+      LAUNCH(e, "mesh_write", (k_mesh_blocks<true, SRC>), dim3(std::min(8192, div_up(end - first, kMeshWaves))), dim3(64 * kMeshWaves),
+             sc, mp, list, nPtr, blockCount, (const uint32_t *)blockOffset, e->meshTris, keep, src);
+    }
   }
   const hipError_t err = hipStreamSynchronize(e->stream);  // (also before the scratch goes)
   if (st == DSR_OK && err != hipSuccess) st = fail(DSR_E_DEVICE, hipGetErrorString(err));
   if (st == DSR_OK) e->meshCount = keep;
-  else { (void)hipFree(e->meshTris); e->meshTris = nullptr; }
+  else {
+    (void)hipFree(e->meshTris); e->meshTris = nullptr;
+    if (e->meshClr) { (void)hipFree(e->meshClr); e->meshClr = nullptr; }
+  }
   return st;
 }
 int no_prep(int, int, MeshResident &) { return DSR_OK; }
+long long host_store_slots(const dsr_engine *e) { return (long long)e->hostSlabs.size() * e->scene.slabBlocks; }
+template <bool COLOUR> int mesh_resident(dsr_engine *e, uint64_t *n_triangles);
+template <bool COLOUR> int mesh_complete(dsr_engine *e, uint64_t *n_triangles);
 }  // namespace
 }  // extern "C++"
 
@@ -1751,7 +1774,12 @@ int dsr_mesh_free(dsr_engine *e) {
 }
 
 // ITMMeshingEngine::MeshScene (an offline dump: host synchronisation is fine here)
-int dsr_mesh_scene(dsr_engine *e, uint64_t *n_triangles) {
+int dsr_mesh_scene(dsr_engine *e, uint64_t *n_triangles) { return mesh_resident<false>(e, n_triangles); }
+
+extern "C++" {
+namespace {
+template <bool COLOUR>
+int mesh_resident(dsr_engine *e, uint64_t *n_triangles) {
   CHECK_E(e);
   int st = mesh_release(e);
   if (st) return st;
@@ -1768,20 +1796,23 @@ int dsr_mesh_scene(dsr_engine *e, uint64_t *n_triangles) {
   if (n <= 0) return DSR_OK;
   // ITMMesh: noMaxTriangles = maxBlocks * 32; the append keeps the first noMaxTriangles - 1
   const unsigned long long cap = (unsigned long long)e->noBlocks * 32ull - 1ull;
-  st = mesh_from_list<MeshResident>(e, e->scene, e->decayCand, nPtr, n, e->tileSums, cap, n, no_prep);
+  st = mesh_from_list<MeshResident, COLOUR>(e, e->scene, e->decayCand, nPtr, n, e->tileSums, cap, n, no_prep);
   if (st == DSR_OK && n_triangles) *n_triangles = e->meshCount;
   return st;
 }
+}  // namespace
+}  // extern "C++"
 
 // ---- the complete mesh of a swapping engine (include/dsr_mesh.h, k_mesh_complete.h; builder-defined)
 
 int32_t dsr_mesh_abi_version(void) { return DSR_MESH_ABI_VERSION; }
 
-namespace {
-long long host_store_slots(const dsr_engine *e) { return (long long)e->hostSlabs.size() * e->scene.slabBlocks; }
-}  // namespace
+int dsr_mesh_scene_complete(dsr_engine *e, uint64_t *n_triangles) { return mesh_complete<false>(e, n_triangles); }
 
-int dsr_mesh_scene_complete(dsr_engine *e, uint64_t *n_triangles) {
+extern "C++" {
+namespace {
+template <bool COLOUR>
+int mesh_complete(dsr_engine *e, uint64_t *n_triangles) {
   // (no deferred render is queued here: it reads the scene, as this call does, and stays pending)
   CHECK_E_NOFLUSH(e);
   int st = mesh_release(e);
@@ -1809,35 +1840,38 @@ int dsr_mesh_scene_complete(dsr_engine *e, uint64_t *n_triangles) {
   if (n <= 0) return DSR_OK;
   const unsigned long long cap = (unsigned long long)std::max(e->noBlocks, n) * 32ull - 1ull;
   if (!e->scene.swapStored) {  // nothing is ever stored: the resident mesher over the same list
-    st = mesh_from_list<MeshResident>(e, sc, list, nPtr, n, tileSums, cap, n, no_prep);
+    st = mesh_from_list<MeshResident, COLOUR>(e, sc, list, nPtr, n, tileSums, cap, n, no_prep);
   } else {
     if (head[1] < 0 || head[1] > host_store_slots(e)) return fail(DSR_E_DEVICE, "host store inconsistent");
     // The pool: a chunk of the list reaches at most 8 entries per listed one, and never more than the store holds.  A chunk of
     // 2^17 entries bounds it at 1 GiB; a map with fewer stored entries than that takes ONE chunk whatever its size, and only a
-    // mesh of several chunks fetches planes twice (count pass, write pass).  env DSR_MESH_CHUNK: the chunk (tests).
-    int chunk = 1 << 17;
+    // mesh of several chunks fetches planes twice (count pass, write pass).  env DSR_MESH_CHUNK: the chunk (tests).  With colours a
+    // plane of the pool is a slot of 3 KiB (sdf + colour words), so a third of that chunk keeps the bound.
+    using Pooled = std::conditional_t<COLOUR, MeshPooledColour, MeshPooled>;
+    constexpr size_t kSlot = COLOUR ? kColourSlotBytes : kPlaneBytes;
+    int chunk = (1 << 17) / (int)(kSlot / kPlaneBytes);
     if (const char *c = getenv("DSR_MESH_CHUNK")) chunk = std::max(1, atoi(c));
     if (head[1] <= 8ll * chunk) chunk = std::max(chunk, n);
     const int poolCap = (int)std::min<long long>(head[1], 8ll * std::min(chunk, n));
     int32_t *planeOf = nullptr, *poolIds = nullptr, *poolCtr = nullptr;
     uint8_t *pool = nullptr;
     if ((st = scratch.get(&planeOf, (size_t)e->E)) || (st = scratch.get(&poolIds, (size_t)poolCap)) ||
-        (st = scratch.get(&poolCtr, 2)) || (st = scratch.get(&pool, (size_t)poolCap * kPlaneBytes)))
+        (st = scratch.get(&poolCtr, 2)) || (st = scratch.get(&pool, (size_t)poolCap * kSlot)))
       return st;
     MeshP mp; mp.voxelSize = e->s.voxel_size; mp.hashMask = (uint32_t)(e->noBuckets - 1); mp.noBuckets = e->noBuckets;
     const int noSlots = (int)std::min<long long>(host_store_slots(e), 0x7fffffff);
     HIP_TRY(hipMemsetAsync(poolCtr, 0, 8, e->stream));  // (the overflow flag, poolCtr[1], is sticky over the chunks)
-    auto prep = [&](int first, int end, MeshPooled &src) -> int {
+    auto prep = [&](int first, int end, Pooled &src) -> int {
       src.planeOf = planeOf; src.pool = pool; src.firstItem = first; src.endItem = end;
       HIP_TRY(hipMemsetAsync(planeOf, 0xff, (size_t)e->E * 4, e->stream));
       HIP_TRY(hipMemsetAsync(poolCtr, 0, 4, e->stream));
       LAUNCH(e, "mesh_mark", k_mesh_mark, dim3(div_up((long long)(end - first) * 8, 256)), dim3(256), sc, mp, (const int32_t *)list,
              nPtr, first, end, planeOf, poolIds, poolCap, poolCtr);
-      LAUNCH(e, "mesh_gather", k_mesh_gather, dim3(std::max(1, std::min(1024, div_up(poolCap, 4)))), dim3(256), sc, (int)e->s.max_w,
+      LAUNCH(e, "mesh_gather", (k_mesh_gather<COLOUR>), dim3(std::max(1, std::min(1024, div_up(poolCap, 4)))), dim3(256), sc, (int)e->s.max_w,
              e->noBlocks, noSlots, (const int32_t *)poolIds, (const int32_t *)poolCtr, poolCap, pool);
       return DSR_OK;
     };
-    st = mesh_from_list<MeshPooled>(e, sc, list, nPtr, n, tileSums, cap, chunk, prep);
+    st = mesh_from_list<Pooled, COLOUR>(e, sc, list, nPtr, n, tileSums, cap, chunk, prep);
     if (st == DSR_OK) {
       int32_t over = 0;
       HIP_TRY(hipMemcpy(&over, poolCtr + 1, 4, hipMemcpyDeviceToHost));
@@ -1847,6 +1881,8 @@ int dsr_mesh_scene_complete(dsr_engine *e, uint64_t *n_triangles) {
   if (st == DSR_OK && n_triangles) *n_triangles = e->meshCount;
   return st;
 }
+}  // namespace
+}  // extern "C++"
 
 int dsr_save_scene_to_mesh_complete(dsr_engine *e, const char *path) {
   int st = dsr_mesh_scene_complete(e, nullptr);
@@ -1925,6 +1961,126 @@ int dsr_save_scene_to_mesh(dsr_engine *e, const char *path) {
   int st = dsr_mesh_scene(e, nullptr);
   if (st == DSR_OK) st = dsr_mesh_write_obj(e, path);
   if (e) (void)dsr_mesh_free(e);
+  return st;
+}
+
+// ---- coloured meshes (include/dsr_mesh.h; builder-defined)
+
+int dsr_mesh_scene_coloured(dsr_engine *e, int complete, uint64_t *n_triangles) {
+  const int st = complete ? mesh_complete<true>(e, n_triangles) : mesh_resident<true>(e, n_triangles);
+  if (st == DSR_OK) e->meshColoured = true;  // (also a mesh of no triangles: get_colours(0, 0) and the PLY header treat it as coloured)
+  return st;
+}
+
+int dsr_mesh_get_colours(dsr_engine *e, dsr_triangle_colour *out, uint64_t first, uint64_t count) {
+  CHECK_E(e);
+  if (!out && count) return fail(DSR_E_ARG, "null");
+  if (!e->meshColoured)
+    return fail(DSR_E_ARG, e->meshCount ? "the current mesh has no colours (dsr_mesh_scene_coloured makes one that has)" : "no mesh");
+  if (first + count > e->meshCount) return fail(DSR_E_ARG, "triangle range outside the mesh");
+  if (count) {
+    HIP_TRY(hipMemcpyAsync(out, e->meshClr + first, (size_t)count * sizeof(dsr_triangle_colour), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+  }
+  return DSR_OK;
+}
+
+extern "C++" {
+namespace {
+// the current mesh, chunk by chunk: geometry and (wantColours) colours of triangles first .. first + cnt - 1 to `emit`
+template <class EMIT>
+int mesh_for_each_chunk(dsr_engine *e, bool wantColours, EMIT emit) {
+  const uint64_t chunk = 1u << 20;
+  std::vector<dsr_triangle> tris((size_t)std::min<uint64_t>(chunk, e->meshCount));
+  std::vector<dsr_triangle_colour> clrs(wantColours ? tris.size() : 0);
+  int st = DSR_OK;
+  for (uint64_t first = 0; first < e->meshCount && st == DSR_OK; first += chunk) {
+    const uint64_t cnt = std::min<uint64_t>(chunk, e->meshCount - first);
+    st = dsr_mesh_get(e, tris.data(), first, cnt);
+    if (st == DSR_OK && wantColours) st = dsr_mesh_get_colours(e, clrs.data(), first, cnt);
+    if (st == DSR_OK) emit(tris.data(), wantColours ? clrs.data() : nullptr, cnt);
+  }
+  return st;
+}
+bool ends_in_ply(const char *path) {
+  const size_t n = strlen(path);
+  return n >= 4 && path[n - 4] == '.' && (path[n - 3] | 0x20) == 'p' && (path[n - 2] | 0x20) == 'l' && (path[n - 1] | 0x20) == 'y';
+}
+}  // namespace
+}  // extern "C++"
+
+int dsr_mesh_write_obj_coloured(dsr_engine *e, const char *path) {
+  CHECK_E(e);
+  if (!path) return fail(DSR_E_ARG, "null path");
+  if (!e->meshColoured)
+    return fail(DSR_E_ARG, e->meshCount ? "the current mesh has no colours (dsr_mesh_scene_coloured makes one that has)" : "no mesh");
+  FILE *f = fopen(path, "w+");
+  if (!f) return fail(DSR_E_ARG, "cannot open the OBJ file for writing");
+  int st = mesh_for_each_chunk(e, true, [&](const dsr_triangle *t, const dsr_triangle_colour *c, uint64_t cnt) {
+    for (uint64_t i = 0; i < cnt; ++i) {
+      const float *p[3] = {t[i].p0, t[i].p1, t[i].p2};
+      const uint8_t *q[3] = {c[i].c0, c[i].c1, c[i].c2};
+      for (int k = 0; k < 3; ++k)
+        fprintf(f, "v %f %f %f %f %f %f\n", p[k][0], p[k][1], p[k][2], (float)q[k][0] / 255.0f, (float)q[k][1] / 255.0f,
+                (float)q[k][2] / 255.0f);
+    }
+  });
+  for (uint64_t i = 0; i < e->meshCount && st == DSR_OK; i++)
+    fprintf(f, "f %llu %llu %llu\n", (unsigned long long)(i * 3 + 2 + 1), (unsigned long long)(i * 3 + 1 + 1),
+            (unsigned long long)(i * 3 + 0 + 1));
+  const bool bad = ferror(f) != 0;
+  if ((fclose(f) != 0 || bad) && st == DSR_OK) st = fail(DSR_E_ARG, "writing the OBJ file failed");
+  return st;
+}
+
+int dsr_mesh_write_ply(dsr_engine *e, const char *path) {
+  CHECK_E(e);
+  if (!path) return fail(DSR_E_ARG, "null path");
+  const bool colours = e->meshColoured;
+  const uint64_t n = e->meshCount;
+  if (n * 3 > 0x7fffffffull) return fail(DSR_E_ARG, "too many vertices for the int indices of a PLY face");
+  FILE *f = fopen(path, "wb");
+  if (!f) return fail(DSR_E_ARG, "cannot open the PLY file for writing");
+  fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %llu\nproperty float x\nproperty float y\nproperty float z\n",
+          (unsigned long long)(n * 3));
+  if (colours) fprintf(f, "property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\n");
+  fprintf(f, "element face %llu\nproperty list uchar int vertex_indices\nend_header\n", (unsigned long long)n);
+  std::vector<uint8_t> rec;
+  int st = mesh_for_each_chunk(e, colours, [&](const dsr_triangle *t, const dsr_triangle_colour *c, uint64_t cnt) {
+    const size_t vb = colours ? 16 : 12;
+    rec.resize((size_t)cnt * 3 * vb);
+    for (uint64_t i = 0; i < cnt; ++i) {
+      const float *p[3] = {t[i].p0, t[i].p1, t[i].p2};
+      for (int k = 0; k < 3; ++k) {
+        uint8_t *o = rec.data() + ((size_t)i * 3 + k) * vb;
+        memcpy(o, p[k], 12);
+        if (colours) memcpy(o + 12, k == 0 ? c[i].c0 : (k == 1 ? c[i].c1 : c[i].c2), 4);
+      }
+    }
+    fwrite(rec.data(), 1, rec.size(), f);
+  });
+  const uint64_t faceChunk = 1u << 16;
+  rec.resize((size_t)std::min<uint64_t>(faceChunk, n) * 13);
+  for (uint64_t first = 0; first < n && st == DSR_OK; first += faceChunk) {
+    const uint64_t cnt = std::min<uint64_t>(faceChunk, n - first);
+    for (uint64_t i = 0; i < cnt; ++i) {
+      uint8_t *o = rec.data() + (size_t)i * 13;
+      const int32_t idx[3] = {(int32_t)((first + i) * 3 + 2), (int32_t)((first + i) * 3 + 1), (int32_t)((first + i) * 3)};
+      o[0] = 3;
+      memcpy(o + 1, idx, 12);
+    }
+    fwrite(rec.data(), 1, (size_t)cnt * 13, f);
+  }
+  const bool bad = ferror(f) != 0;
+  if ((fclose(f) != 0 || bad) && st == DSR_OK) st = fail(DSR_E_ARG, "writing the PLY file failed");
+  return st;
+}
+
+int dsr_save_scene_to_mesh_coloured(dsr_engine *e, const char *path, int complete) {
+  if (e && !path) return fail(DSR_E_ARG, "null path");
+  int st = dsr_mesh_scene_coloured(e, complete, nullptr);
+  if (st == DSR_OK) st = ends_in_ply(path) ? dsr_mesh_write_ply(e, path) : dsr_mesh_write_obj_coloured(e, path);
+  if (e) (void)mesh_release(e);
   return st;
 }
 

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "dsr_device.h"
+#include "../../include/dsr_mesh.h"
 #include "../../include/dsr_track.h"
 
 using namespace dsr;
@@ -133,6 +134,8 @@ struct dsr_engine {
   Mat4 fvM;
   float fvProj[4] = {0, 0, 0, 0};
   dsr_triangle *meshTris = nullptr;  // current mesh (dsr_mesh_scene), device
+  dsr_triangle_colour *meshClr = nullptr;  // its vertex colours (dsr_mesh_scene_coloured), else null
+  bool meshColoured = false;  // the current mesh was made by dsr_mesh_scene_coloured (meshClr is null when it has no triangles)
   uint64_t meshCount = 0;
 
   // view

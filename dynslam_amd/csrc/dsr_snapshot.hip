@@ -538,6 +538,8 @@ int load_impl(dsr_engine *e, const char *path, const dsr_snapshot *snap) {
   e->sidePending = false;
   if (e->device >= 0 && e->device < 64 && g_ioStream[e->device]) HIP_TRY(hipStreamSynchronize(g_ioStream[e->device]));
   if (e->meshTris) { (void)hipFree(e->meshTris); e->meshTris = nullptr; }
+  if (e->meshClr) { (void)hipFree(e->meshClr); e->meshClr = nullptr; }
+  e->meshColoured = false;
   e->meshCount = 0;
   { int st = engine_reset(e); if (st) return st; }
 

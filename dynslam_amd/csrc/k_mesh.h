@@ -12,8 +12,12 @@
 //   pass 2  k_mesh_blocks<true, SRC>: same staging, a wave prefix over the lanes' counts gives every cell
 //           its slot; vertices by sdfInterp on the cell edges, scaled to metres.
 // Arithmetic follows ITMMeshingEngine.h (findPointNeighbors, sdfInterp, buildVertList).
+//   pass 2, coloured  k_mesh_blocks<true, MeshColoured<SRC>> (include/dsr_mesh.h, builder-defined): pass 2 with a
+//           second 9x9x9 lattice, of the (r, g, b, w_color) words of the same 8 blocks, beside the sdf one; next to every triangle
+//           the colours of its three vertices (vertex_colour), at the same slot.  Every other instantiation compiles without that part.
 #pragma once
 #include "dsr_device.h"
+#include "../../include/dsr_mesh.h"
 
 #define MC_TABLE_ATTR __constant__ static const
 #include "mc_tables.h"
@@ -38,11 +42,35 @@ __device__ __forceinline__ float3 sdf_interp(float3 p1, float3 p2, float v1, flo
   return make_float3(p1.x + t * (p2.x - p1.x), p1.y + t * (p2.y - p1.y), p1.z + t * (p2.z - p1.z));
 }
 
+// The colour of the vertex sdf_interp puts on the edge between corners a and b: t by sdf_interp's own decisions,
+// in its order; words are (r, g, b, w_color), lowest byte first; the result is (r, g, b, alpha).  No colour ever fused at either
+// corner: 0, alpha included; at one of them: the other's; else every channel (uint8_t)(ca + t * (cb - ca) + 0.5f).
+__device__ __forceinline__ uint32_t vertex_colour(float va, float vb, uint32_t wordA, uint32_t wordB) {
+  float t;
+  if (fabsf(0.0f - va) < 0.00001f) t = 0.0f;
+  else if (fabsf(0.0f - vb) < 0.00001f) t = 1.0f;
+  else if (fabsf(va - vb) < 0.00001f) t = 0.0f;
+  else t = (0.0f - va) / (vb - va);
+  const bool hasA = (wordA >> 24) != 0, hasB = (wordB >> 24) != 0;
+  if (!hasA && !hasB) return 0u;
+  if (!hasB) return wordA | 0xff000000u;
+  if (!hasA) return wordB | 0xff000000u;
+  uint32_t out = 0xff000000u;
+#pragma unroll
+  for (int sh = 0; sh < 24; sh += 8) {
+    const float ca = (float)((wordA >> sh) & 0xffu), cb = (float)((wordB >> sh) & 0xffu);
+    out |= (uint32_t)(uint8_t)(ca + t * (cb - ca) + 0.5f) << sh;
+  }
+  return out;
+}
+
 // WHERE THE SDF PLANE OF A BLOCK LIES is a policy of the kernel.  A policy answers, for a table entry whose position matches:
-// does it own voxel data (owns), and under which code (locate) (an int the wave keeps in LDS; -1 = none); for a code: the plane's address; and
+// does it own voxel data (owns), and under which code (locate) (an int the wave keeps in LDS; -1 = none); for a code: the plane's address
+// (sdf_plane; clr_plane: the 2 KiB plane of colour words, which only a coloured write pass asks for); and
 // which part of the list this launch covers.  MeshResident is dsr_mesh_scene's: the entries with ptr >= 0, code = ptr, the plane
 // inside the block array.  k_mesh_complete.h has the one that also knows the host store.
 struct MeshResident {
+  static constexpr bool kColour = false;
   __device__ __forceinline__ int first() const { return 0; }
   __device__ __forceinline__ int end(int n) const { return n; }
   __device__ __forceinline__ bool owns(const SceneP &, uint32_t, int ptr) const { return ptr >= 0; }
@@ -51,6 +79,15 @@ struct MeshResident {
   __device__ __forceinline__ const uint8_t *sdf_plane(const SceneP &s, int code) const {
     return s.vba + (size_t)code * kBlockBytes + kOffSdf;
   }
+  __device__ __forceinline__ const uint8_t *clr_plane(const SceneP &s, int code) const {
+    return s.vba + (size_t)code * kBlockBytes + kOffClr;
+  }
+};
+// ... and a policy (one with clr_plane) whose write pass also leaves the vertex colours of triangle `slot` in colours[slot]
+template <class SRC>
+struct MeshColoured : SRC {
+  static constexpr bool kColour = true;
+  dsr_triangle_colour *colours;
 };
 
 template <bool WRITE, class SRC = MeshResident>
@@ -61,6 +98,12 @@ __global__ __launch_bounds__(64 * kMeshWaves) void k_mesh_blocks(SceneP s, MeshP
                                                                  dsr_triangle *__restrict__ out, unsigned long long cap, SRC src) {
   __shared__ int s_lat[kMeshWaves][9 * 9 * 9];
   __shared__ int s_nbr[kMeshWaves][8];
+  constexpr bool COLOUR = WRITE && SRC::kColour;
+  uint32_t *clat = nullptr;  // the colour lattice of this wave (2 916 B)
+  if constexpr (COLOUR) {
+    __shared__ uint32_t s_clr[kMeshWaves][9 * 9 * 9];
+    clat = s_clr[threadIdx.x >> 6];
+  }
   const int n = src.end(*nPtr);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int *lat = s_lat[wave];
@@ -90,8 +133,9 @@ __global__ __launch_bounds__(64 * kMeshWaves) void k_mesh_blocks(SceneP s, MeshP
       if (src.has(ptr)) {
         const int lin = (cx & 7) + ((cy & 7) << 3) + ((cz & 7) << 6);
         v = (int)*reinterpret_cast<const short *>(src.sdf_plane(s, ptr) + lin * 2);
+        if constexpr (COLOUR) clat[c] = *reinterpret_cast<const uint32_t *>(src.clr_plane(s, ptr) + lin * 4);
       }
-      lat[c] = v;
+      lat[c] = v;  // (a cell with a missing corner yields no triangle: that corner's colour word is never read)
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -138,6 +182,7 @@ __global__ __launch_bounds__(64 * kMeshWaves) void k_mesh_blocks(SceneP s, MeshP
         const int off[8] = {o, o + 1, o + 10, o + 9, o + 81, o + 82, o + 91, o + 90};
         for (int k = 0; kMcTriTable[ci][k] != -1; k += 3) {
           float3 v[3];
+          [[maybe_unused]] uint32_t vc[3];
 #pragma unroll
           for (int j = 0; j < 3; ++j) {
             const int e = kMcTriTable[ci][k + j];
@@ -150,12 +195,17 @@ __global__ __launch_bounds__(64 * kMeshWaves) void k_mesh_blocks(SceneP s, MeshP
             const float va = sdf_to_float((float)lat[off[a]]), vb = sdf_to_float((float)lat[off[b]]);
             const float3 q = sdf_interp(pa, pb, va, vb);
             v[j] = make_float3(q.x * mp.voxelSize, q.y * mp.voxelSize, q.z * mp.voxelSize);
+            if constexpr (COLOUR) vc[j] = vertex_colour(va, vb, clat[off[a]], clat[off[b]]);
           }
           // triangles[n] = t; if (n < noMaxTriangles - 1) n++;  => the first cap triangles survive
           if (slot < cap) {
             float *t = reinterpret_cast<float *>(out + slot);
             t[0] = v[0].x; t[1] = v[0].y; t[2] = v[0].z; t[3] = v[1].x; t[4] = v[1].y; t[5] = v[1].z;
             t[6] = v[2].x; t[7] = v[2].y; t[8] = v[2].z;
+            if constexpr (COLOUR) {
+              uint32_t *c = reinterpret_cast<uint32_t *>(src.colours + slot);
+              c[0] = vc[0]; c[1] = vc[1]; c[2] = vc[2];
+            }
           }
           slot++;
         }

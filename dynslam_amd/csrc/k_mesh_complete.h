@@ -12,6 +12,9 @@
 //   k_mesh_gather  a wave per pool plane, shaped like k_swapin_fetch: 16 B per lane, coalesced — the sdf plane of the host copy
 //                  and, for a pending merge, its w_depth plane and both planes of the device block; one merged 1 KiB plane out;
 //   k_mesh_blocks<WRITE, MeshPooled>  the mesher of k_mesh.h with one indirection: device block or pool plane.
+// With colours (dsr_mesh_scene_coloured) a pool slot is the sdf plane and the 2 KiB plane of colour words behind it:
+// k_mesh_gather<true> also brings the colour plane over the link, 2 x 16 B per lane, and merges it by combineVoxelColorInformation for
+// a pending merge; MeshPooledColour serves both planes to k_mesh_blocks<true, MeshColoured<MeshPooledColour>>.
 // Nothing here writes the scene: table, swap state, host store and counters are read only.
 #pragma once
 #include "k_decay.h"
@@ -20,7 +23,9 @@
 
 namespace dsr {
 
-constexpr int kPlaneBytes = kBlockSize3 * 2;  // one sdf plane
+constexpr int kPlaneBytes = kBlockSize3 * 2;     // one sdf plane
+constexpr int kClrPlaneBytes = kBlockSize3 * 4;  // one plane of (r, g, b, w_color) words
+constexpr int kColourSlotBytes = kPlaneBytes + kClrPlaneBytes;  // a pool slot of the coloured mesher
 
 // the ordered list of the entries that own voxel data (k_decay.h entry_listed<true>)
 __global__ __launch_bounds__(kTileThreads) void k_owning_count(SceneP s, int noTotalEntries, int2 *__restrict__ tileSums) {
@@ -39,6 +44,7 @@ __device__ __forceinline__ bool plane_from_store(const SceneP &s, uint32_t entry
 }
 
 struct MeshPooled {
+  static constexpr bool kColour = false;
   const int32_t *planeOf;  // per entry: its plane of the pool, -1: none (in this chunk)
   const uint8_t *pool;
   int firstItem, endItem;  // the chunk of the list
@@ -54,6 +60,16 @@ struct MeshPooled {
   __device__ __forceinline__ bool has(int code) const { return code != -1; }
   __device__ __forceinline__ const uint8_t *sdf_plane(const SceneP &s, int code) const {
     return code >= 0 ? s.vba + (size_t)code * kBlockBytes + kOffSdf : pool + (size_t)(-2 - code) * kPlaneBytes;
+  }
+};
+
+// ... with the colour plane behind the sdf plane of every pool slot
+struct MeshPooledColour : MeshPooled {
+  __device__ __forceinline__ const uint8_t *sdf_plane(const SceneP &s, int code) const {
+    return code >= 0 ? s.vba + (size_t)code * kBlockBytes + kOffSdf : pool + (size_t)(-2 - code) * kColourSlotBytes;
+  }
+  __device__ __forceinline__ const uint8_t *clr_plane(const SceneP &s, int code) const {
+    return code >= 0 ? s.vba + (size_t)code * kBlockBytes + kOffClr : pool + (size_t)(-2 - code) * kColourSlotBytes + kPlaneBytes;
   }
 };
 
@@ -88,6 +104,9 @@ __global__ __launch_bounds__(256) void k_mesh_mark(SceneP s, MeshP mp, const int
 // pool plane i <- the sdf plane entry poolIds[i] has after its next swap-in.  Lane l: voxels 8 l .. 8 l + 7 (16 B of sdf, 8 B of
 // w_depth).  The second fence (the host checked the store): with a slot out of range the stored copy counts as absent — the device
 // block alone, or "never observed" without one — as in k_merged_block; a block index out of range likewise.
+// COLOUR: slots of kColourSlotBytes; the colour plane by the same rule and behind the same fences (neither a stored copy nor a device
+// block: words of 0, "no colour ever fused"), lane l the words 4 l .. 4 l + 3 of either half.
+template <bool COLOUR = false>
 __global__ __launch_bounds__(256) void k_mesh_gather(SceneP s, int maxW, int noBlocks, int noSlots,
                                                      const int32_t *__restrict__ poolIds, const int32_t *__restrict__ ctrs, int poolCap,
                                                      uint8_t *__restrict__ pool) {
@@ -123,7 +142,36 @@ __global__ __launch_bounds__(256) void k_mesh_gather(SceneP s, int maxW, int noB
         r = make_uint4(o[0], o[1], o[2], o[3]);
       }
     }
-    reinterpret_cast<uint4 *>(pool + (size_t)i * kPlaneBytes)[lane] = r;
+    constexpr int kSlot = COLOUR ? kColourSlotBytes : kPlaneBytes;
+    reinterpret_cast<uint4 *>(pool + (size_t)i * kSlot)[lane] = r;
+    if constexpr (COLOUR) {
+      const uint4 *host = slotOk ? reinterpret_cast<const uint4 *>(host_block(s, slot) + kOffClr) : nullptr;
+      const uint4 *blk = blockOk ? reinterpret_cast<const uint4 *>(s.vba + (size_t)ptr * kBlockBytes + kOffClr) : nullptr;
+      uint4 *dst = reinterpret_cast<uint4 *>(pool + (size_t)i * kSlot + kPlaneBytes);
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        uint4 c = make_uint4(0u, 0u, 0u, 0u);
+        if (!host) {
+          if (blk) c = blk[k * 64 + lane];
+        } else {
+          c = host[k * 64 + lane];
+          if (blk) {  // a pending merge: combine_block_lane's colour rule
+            const uint4 d = blk[k * 64 + lane];
+            const uint32_t hc[4] = {c.x, c.y, c.z, c.w}, dc[4] = {d.x, d.y, d.z, d.w};
+            uint32_t o[4];
+#pragma unroll
+            for (int x = 0; x < 4; ++x) {
+              const uchar4 sc = make_uchar4(hc[x] & 0xff, (hc[x] >> 8) & 0xff, (hc[x] >> 16) & 0xff, hc[x] >> 24);
+              const uchar4 dv = make_uchar4(dc[x] & 0xff, (dc[x] >> 8) & 0xff, (dc[x] >> 16) & 0xff, dc[x] >> 24);
+              const uchar4 m = combine_voxel_colour(sc, dv, maxW);  // (w_color of the stored copy 0: the device word)
+              o[x] = (uint32_t)m.x | ((uint32_t)m.y << 8) | ((uint32_t)m.z << 16) | ((uint32_t)m.w << 24);
+            }
+            c = make_uint4(o[0], o[1], o[2], o[3]);
+          }
+        }
+        dst[k * 64 + lane] = c;
+      }
+    }
   }
 }
 

@@ -726,6 +726,38 @@ class EngineCore:
     def save_scene_to_mesh_complete(self, path):
         self._check(self._mesh_api().save_scene_to_mesh_complete(self._h, str(path).encode()))
 
+    # ---- coloured meshes (include/dsr_mesh.h; builder-defined)
+    def mesh_scene_coloured(self, complete=False):
+        """mesh_scene (complete=False) or mesh_scene_complete (complete=True) with the colour of every vertex
+        (dsr_mesh_scene_coloured).  Returns (triangles float32 [n, 3, 3], RGBA uint8 [n, 3, 4]); alpha 0: no colour was ever fused
+        at that vertex.  mesh_write_obj_coloured / mesh_write_ply / mesh_free serve the result."""
+        n = C.c_uint64(0)
+        self._check(self._mesh_api().mesh_scene_coloured(self._h, int(bool(complete)), C.byref(n)))
+        tris = np.empty((n.value, 3, 3), np.float32)
+        clrs = np.empty((n.value, 3, 4), np.uint8)
+        if n.value:
+            self._check(self.api.mesh_get(self._h, tris.ctypes.data_as(C.c_void_p), 0, n.value))
+            clrs[...] = self.mesh_get_colours(0, n.value)
+        return tris, clrs
+
+    def mesh_get_colours(self, first, count):
+        """RGBA uint8 [count, 3, 4] of the current mesh; raises when it was made without colours."""
+        out = np.empty((int(count), 3, 4), np.uint8)
+        self._check(self._mesh_api().mesh_get_colours(self._h, out.ctypes.data_as(C.c_void_p), int(first), int(count)))
+        return out
+
+    def mesh_write_obj_coloured(self, path):
+        """The current (coloured) mesh as an OBJ with "v x y z r g b" lines."""
+        self._check(self._mesh_api().mesh_write_obj_coloured(self._h, str(path).encode()))
+
+    def mesh_write_ply(self, path):
+        """The current mesh, coloured or not, as a binary little-endian PLY."""
+        self._check(self._mesh_api().mesh_write_ply(self._h, str(path).encode()))
+
+    def save_scene_to_mesh_coloured(self, path, complete=False):
+        """Coloured mesh, written as PLY when the path ends in .ply, else as a coloured OBJ; the mesh is freed."""
+        self._check(self._mesh_api().save_scene_to_mesh_coloured(self._h, str(path).encode(), int(bool(complete))))
+
     def dump_merged_block(self, entry):
         """For tests: the block of a table entry as the complete mesher sees it (dsr_dump_merged_block), None if it owns no data."""
         out = np.empty(BLOCK_SIZE3, VOXEL_DTYPE)
@@ -938,11 +970,14 @@ class InfiniTamDriver:
     def Reset(self):
         self.core.reset_scene()
 
-    def SaveSceneToMesh(self, path, complete=False):
+    def SaveSceneToMesh(self, path, complete=False, coloured=False):
         """ITMMainEngine::SaveSceneToMesh as called by DynSlam::SaveStaticMap (DynSlam.cpp:188-196)
         and, per instance, InstanceReconstructor::SaveObjectToMesh (InstanceReconstructor.cpp:736-763).
-        complete=True (builder-defined, include/dsr_mesh.h): the whole map of a swapping engine, host-store blocks included."""
-        if complete:
+        complete=True (builder-defined, include/dsr_mesh.h): the whole map of a swapping engine, host-store blocks included.
+        coloured=True (builder-defined): per-vertex colour; a PLY when the path ends in .ply, else an OBJ with "v x y z r g b"."""
+        if coloured:
+            self.core.save_scene_to_mesh_coloured(path, complete)
+        elif complete:
             self.core.save_scene_to_mesh_complete(path)
         else:
             self.core.save_scene_to_mesh(path)

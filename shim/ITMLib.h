@@ -39,6 +39,12 @@ int dsr_snapshot_load(dsr_engine *e, const char *path) __attribute__((weak));
 // ... and the complete mesher's (include/dsr_mesh.h): SaveCompleteSceneToMesh / MeshSceneComplete throw on a library without them
 int dsr_mesh_scene_complete(dsr_engine *e, uint64_t *n_triangles) __attribute__((weak));
 int dsr_save_scene_to_mesh_complete(dsr_engine *e, const char *path) __attribute__((weak));
+// ... and the coloured meshes' (DSR_MESH_ABI_VERSION 2): SaveColouredSceneToMesh throws on a library without them
+int dsr_mesh_scene_coloured(dsr_engine *e, int complete, uint64_t *n_triangles) __attribute__((weak));
+int dsr_mesh_get_colours(dsr_engine *e, dsr_triangle_colour *out, uint64_t first, uint64_t count) __attribute__((weak));
+int dsr_mesh_write_obj_coloured(dsr_engine *e, const char *path) __attribute__((weak));
+int dsr_mesh_write_ply(dsr_engine *e, const char *path) __attribute__((weak));
+int dsr_save_scene_to_mesh_coloured(dsr_engine *e, const char *path, int complete) __attribute__((weak));
 }
 
 #ifndef SDF_BLOCK_SIZE
@@ -615,6 +621,12 @@ class ITMMainEngine {
   void SaveCompleteSceneToMesh(const char *objFileName) {
     if (!dsr_save_scene_to_mesh_complete) throw std::runtime_error("this library has no complete mesher (include/dsr_mesh.h)");
     ITMLib::Engine::dsr_throw(dsr_save_scene_to_mesh_complete(engine_, objFileName));
+  }
+  // BUILDER-DEFINED (include/dsr_mesh.h): the mesh with the colour fused into the map at every vertex; a binary PLY
+  // when the name ends in ".ply", else an OBJ with "v x y z r g b" lines.  complete: as SaveCompleteSceneToMesh.
+  void SaveColouredSceneToMesh(const char *fileName, bool complete = false) {
+    if (!dsr_save_scene_to_mesh_coloured) throw std::runtime_error("this library has no coloured mesher (include/dsr_mesh.h)");
+    ITMLib::Engine::dsr_throw(dsr_save_scene_to_mesh_coloured(engine_, fileName, complete ? 1 : 0));
   }
   // ITMMainEngine::SaveToFile / LoadFromFile: the names of InfiniTAM v3, BUILDER-DEFINED here (the reference's fork of v2 has no
   // checkpoint).  The volume's complete state — scene, render states, tracking maps, view, pose — as a snapshot file
