@@ -458,3 +458,40 @@ def bind_mesh(lib, prefix):
     if ns.mesh_abi_version() != MESH_ABI_VERSION:
         raise ImportError("complete mesher ABI version mismatch (include/dsr_mesh.h)")
     return ns
+
+
+# ---- include/dsr_merge.h: folding one volume into another at a rigid pose.  A table of its own, like the snapshot's (the oracle has none).
+MERGE_ABI_VERSION = 1  # == DSR_MERGE_ABI_VERSION
+
+
+class MergeParams(C.Structure):  # struct dsr_merge_params
+    _fields_ = [("min_w_depth", C.c_int32), ("merge_colour", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+class MergeResult(C.Structure):  # struct dsr_merge_result
+    _fields_ = [("candidate_blocks", C.c_int32), ("blocks_with_data", C.c_int32), ("blocks_allocated", C.c_int32),
+                ("blocks_dropped", C.c_int32), ("voxels_updated", C.c_int64), ("reserved", C.c_int32 * 4)]
+
+
+assert C.sizeof(MergeParams) == 32 and C.sizeof(MergeResult) == 40
+
+MERGE_SIGNATURES = {
+    "merge_abi_version": (C.c_int32, []),
+    "merge_default_params": (None, [C.POINTER(MergeParams)]),
+    "merge_volume": (C.c_int, [_H, _H, C.POINTER(C.c_float), C.POINTER(MergeParams), C.POINTER(MergeResult)]),
+}
+
+
+def bind_merge(lib, prefix):
+    """The merge entry points `prefix + name` in `lib`, or None when the library has none (the CPU oracle)."""
+    if not hasattr(lib, prefix + "merge_volume"):
+        return None
+    ns = SimpleNamespace()
+    for name, (res, args) in MERGE_SIGNATURES.items():
+        fn = getattr(lib, prefix + name)
+        fn.restype = res
+        fn.argtypes = args
+        setattr(ns, name, fn)
+    if ns.merge_abi_version() != MERGE_ABI_VERSION:
+        raise ImportError("merge ABI version mismatch (include/dsr_merge.h)")
+    return ns

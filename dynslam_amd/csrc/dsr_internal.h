@@ -8,6 +8,7 @@
 //   dsr_track.hip     the ICP depth tracker (include/dsr_track.h): its buffers, the launch sequence of one dsr_track, the read-back
 //   dsr_eval.hip      LIDAR-vs-depth accuracy scoring (include/dsr_eval.h): argument checks, the one launch, the read-back
 //   dsr_snapshot.hip  save / load / export / import of an engine's complete state (include/dsr_snapshot.h): the file format, pack / unpack
+//   dsr_merge.hip     folding one volume into another at a rigid pose (include/dsr_merge.h): candidates, ordered insert, the pull
 // Every kernel header (k_*.h) is included by exactly ONE of them: kernels have external linkage.
 #pragma once
 #include <hip/hip_runtime.h>

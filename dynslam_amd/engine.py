@@ -765,6 +765,32 @@ class EngineCore:
         self._check(self._mesh_api().dump_merged_block(self._h, int(entry), _ptr(out), C.byref(present)))
         return out if present.value else None
 
+    # ---- folding another volume into this one (include/dsr_merge.h; builder-defined)
+    def _merge_api(self):
+        if not hasattr(self, "_gapi"):
+            self._gapi = _capi.bind_merge(self.api.lib, self.api.prefix)
+        if self._gapi is None:
+            raise DsrError(_capi.DSR_E_ARG, f"this backend ({self.api.prefix}*) has no include/dsr_merge.h entry points")
+        return self._gapi
+
+    def merge_from(self, src, src_to_dst, min_w_depth=1, merge_colour=True):
+        """Resample the volume of engine `src` into this one (dsr_merge_volume); src_to_dst: 4x4, metres of src's world -> metres
+        of this engine's world (row-major numpy, as every pose here).  Returns the result as a dict; raises OutOfBlocksError —
+        with the dict as its `result` — when this engine ran out of blocks (what fitted is merged and kept)."""
+        m = np.ascontiguousarray(np.asarray(src_to_dst, np.float32).reshape(4, 4).T)  # column-major at the boundary
+        prm = _capi.MergeParams()
+        self._merge_api().merge_default_params(C.byref(prm))
+        prm.min_w_depth, prm.merge_colour = int(min_w_depth), int(bool(merge_colour))
+        res = _capi.MergeResult()
+        status = self._merge_api().merge_volume(self._h, src._h, m.ctypes.data_as(C.POINTER(C.c_float)), C.byref(prm), C.byref(res))
+        out = {k: int(getattr(res, k)) for k in ("candidate_blocks", "blocks_with_data", "blocks_allocated", "blocks_dropped", "voxels_updated")}
+        try:
+            self._check(status)
+        except OutOfBlocksError as err:
+            err.result = out
+            raise
+        return out
+
     def profile_reset(self):
         self._check(self.api.profile_reset(self._h))
 
@@ -981,6 +1007,12 @@ class InfiniTamDriver:
             self.core.save_scene_to_mesh_complete(path)
         else:
             self.core.save_scene_to_mesh(path)
+
+    def MergeFrom(self, other, src_to_dst):
+        """ITMMainEngine::MergeFrom (builder-defined, include/dsr_merge.h): the volume of driver `other` resampled into this one at
+        the rigid transform src_to_dst (other's world -> this world) — what a host calls before it frees a pruned track's
+        reconstruction.  Returns the merge result as a dict."""
+        return self.core.merge_from(other.core, src_to_dst)
 
     def SaveToFile(self, path):
         """ITMMainEngine::SaveToFile of InfiniTAM v3 (builder-defined here: the reference's fork has no checkpoint): the volume's

@@ -27,6 +27,7 @@
 #include "../include/dsr_track.h"
 #include "../include/dsr_snapshot.h"
 #include "../include/dsr_mesh.h"
+#include "../include/dsr_merge.h"
 
 // The tracker's entry points are referenced WEAKLY: a host linked against a library without them (the CPU oracle's orc_* build
 // of the reference's hosts) still links, and ITMTrackingController::Track then throws as it did before the tracker existed.
@@ -45,6 +46,9 @@ int dsr_mesh_get_colours(dsr_engine *e, dsr_triangle_colour *out, uint64_t first
 int dsr_mesh_write_obj_coloured(dsr_engine *e, const char *path) __attribute__((weak));
 int dsr_mesh_write_ply(dsr_engine *e, const char *path) __attribute__((weak));
 int dsr_save_scene_to_mesh_coloured(dsr_engine *e, const char *path, int complete) __attribute__((weak));
+// ... and the volume merge's (include/dsr_merge.h): MergeFrom throws on a library without it
+int dsr_merge_volume(dsr_engine *dst, dsr_engine *src, const float src_to_dst_m[16], const dsr_merge_params *params,
+                     dsr_merge_result *result) __attribute__((weak));
 }
 
 #ifndef SDF_BLOCK_SIZE
@@ -627,6 +631,16 @@ class ITMMainEngine {
   void SaveColouredSceneToMesh(const char *fileName, bool complete = false) {
     if (!dsr_save_scene_to_mesh_coloured) throw std::runtime_error("this library has no coloured mesher (include/dsr_mesh.h)");
     ITMLib::Engine::dsr_throw(dsr_save_scene_to_mesh_coloured(engine_, fileName, complete ? 1 : 0));
+  }
+  // BUILDER-DEFINED (include/dsr_merge.h): the volume of `other` resampled into this one at the rigid transform
+  // src_to_dst (metres of other's world -> metres of this one's), allocating what this volume lacks — what a host calls before it
+  // frees a pruned track's reconstruction.  Throws on exhaustion like Integrate (what fitted is kept).
+  dsr_merge_result MergeFrom(ITMMainEngine &other, const Matrix4f &src_to_dst) {
+    if (!dsr_merge_volume) throw std::runtime_error("this library has no volume merge (include/dsr_merge.h)");
+    dsr_merge_result res;
+    memset(&res, 0, sizeof res);
+    ITMLib::Engine::dsr_throw(dsr_merge_volume(engine_, other.engine_, src_to_dst.m, nullptr, &res));
+    return res;
   }
   // ITMMainEngine::SaveToFile / LoadFromFile: the names of InfiniTAM v3, BUILDER-DEFINED here (the reference's fork of v2 has no
   // checkpoint).  The volume's complete state — scene, render states, tracking maps, view, pose — as a snapshot file
