@@ -495,3 +495,49 @@ def bind_merge(lib, prefix):
     if ns.merge_abi_version() != MERGE_ABI_VERSION:
         raise ImportError("merge ABI version mismatch (include/dsr_merge.h)")
     return ns
+
+
+# ---- include/dsr_align.h: aligning one volume to another (SDF-to-SDF registration).  A table of its own, like the merge's (the oracle has none).
+ALIGN_ABI_VERSION = 1  # == DSR_ALIGN_ABI_VERSION
+ALIGN_MAX_LEVELS = 4   # == DSR_ALIGN_MAX_LEVELS
+
+
+class AlignParams(C.Structure):  # struct dsr_align_params
+    _fields_ = [("no_levels", C.c_int32), ("stride", C.c_int32 * ALIGN_MAX_LEVELS), ("iterations", C.c_int32 * ALIGN_MAX_LEVELS),
+                ("min_w_depth", C.c_int32), ("min_valid_points", C.c_int32), ("termination_threshold", C.c_float),
+                ("max_residual_m", C.c_float), ("reserved", C.c_int32 * 5)]
+
+
+class AlignResult(C.Structure):  # struct dsr_align_result
+    _fields_ = [("evaluations", C.c_int32), ("valid_points", C.c_int32), ("accepted_any", C.c_int32), ("converged", C.c_int32),
+                ("f", C.c_float), ("src_to_dst_m", C.c_float * 16), ("reserved", C.c_int32 * 4)]
+
+
+class AlignLogEntry(C.Structure):  # struct dsr_align_log_entry
+    _fields_ = [("level", C.c_int32), ("iteration", C.c_int32), ("valid_points", C.c_int32), ("accepted", C.c_int32),
+                ("f", C.c_float), ("lambda_", C.c_float), ("step", C.c_float * 6), ("src_to_dst_m", C.c_float * 16)]
+
+
+assert C.sizeof(AlignParams) == 72 and C.sizeof(AlignResult) == 100 and C.sizeof(AlignLogEntry) == 112
+
+ALIGN_SIGNATURES = {
+    "align_abi_version": (C.c_int32, []),
+    "align_default_params": (None, [C.POINTER(AlignParams)]),
+    "align_volume": (C.c_int, [_H, _H, C.POINTER(C.c_float), C.POINTER(AlignParams), C.POINTER(AlignResult),
+                               C.POINTER(AlignLogEntry), C.c_int32, C.POINTER(C.c_int32)]),
+}
+
+
+def bind_align(lib, prefix):
+    """The alignment entry points `prefix + name` in `lib`, or None when the library has none (the CPU oracle)."""
+    if not hasattr(lib, prefix + "align_volume"):
+        return None
+    ns = SimpleNamespace()
+    for name, (res, args) in ALIGN_SIGNATURES.items():
+        fn = getattr(lib, prefix + name)
+        fn.restype = res
+        fn.argtypes = args
+        setattr(ns, name, fn)
+    if ns.align_abi_version() != ALIGN_ABI_VERSION:
+        raise ImportError("align ABI version mismatch (include/dsr_align.h)")
+    return ns

@@ -9,6 +9,7 @@
 //   dsr_eval.hip      LIDAR-vs-depth accuracy scoring (include/dsr_eval.h): argument checks, the one launch, the read-back
 //   dsr_snapshot.hip  save / load / export / import of an engine's complete state (include/dsr_snapshot.h): the file format, pack / unpack
 //   dsr_merge.hip     folding one volume into another at a rigid pose (include/dsr_merge.h): candidates, ordered insert, the pull
+//   dsr_align.hip     aligning one volume to another, SDF to SDF (include/dsr_align.h): the list of blocks, the queued evaluations
 // Every kernel header (k_*.h) is included by exactly ONE of them: kernels have external linkage.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -355,6 +356,34 @@ template <class T>
 int device_alloc(T **p, size_t n) {
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(p), n * sizeof(T)));
   return DSR_OK;
+}
+// ---- shared by the calls that read one volume against another (dsr_merge.hip, dsr_align.hip)
+struct Scratch {  // everything such a call allocates; freed when it leaves
+  const char *what;  // the message of DSR_E_NOMEM
+  std::vector<void *> ptrs;
+  explicit Scratch(const char *what_) : what(what_) {}
+  ~Scratch() { for (void *p : ptrs) (void)hipFree(p); }
+  template <class T>
+  int get(T **p, size_t n) {
+    void *q = nullptr;
+    if (hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); return fail(DSR_E_NOMEM, what); }
+    ptrs.push_back(q);
+    *p = static_cast<T *>(q);
+    return DSR_OK;
+  }
+};
+// finite, affine, and rigid within what the allocation's step bound allows (dsr_engine_create: rays 5 % longer than a rigid pose
+// makes them): no element of R^T R - I beyond 0.1
+inline bool rigid_transform(const float *m) {
+  for (int i = 0; i < 16; ++i) if (!std::isfinite(m[i])) return false;
+  if (m[3] != 0.0f || m[7] != 0.0f || m[11] != 0.0f || m[15] != 1.0f) return false;
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) {
+      double d = 0;
+      for (int k = 0; k < 3; ++k) d += (double)m[a * 4 + k] * (double)m[b * 4 + k];  // columns a and b
+      if (std::fabs(d - (a == b ? 1.0 : 0.0)) > 0.1) return false;
+    }
+  return true;
 }
 }  // namespace dsr_internal
 using dsr_internal::host_range_pinned;

@@ -19,32 +19,6 @@ using namespace dsr_internal;
 
 namespace {
 
-struct Scratch {  // everything the call allocates; freed when it leaves
-  std::vector<void *> ptrs;
-  ~Scratch() { for (void *p : ptrs) (void)hipFree(p); }
-  template <class T>
-  int get(T **p, size_t n) {
-    void *q = nullptr;
-    if (hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); return fail(DSR_E_NOMEM, "merge: out of device memory for the candidate lists"); }
-    ptrs.push_back(q);
-    *p = static_cast<T *>(q);
-    return DSR_OK;
-  }
-};
-
-// rigid within what the allocation's step bound allows (dsr_engine_create: rays 5 % longer than a rigid pose makes them)
-bool rigid(const float *m) {
-  for (int i = 0; i < 16; ++i) if (!std::isfinite(m[i])) return false;
-  if (m[3] != 0.0f || m[7] != 0.0f || m[11] != 0.0f || m[15] != 1.0f) return false;
-  for (int a = 0; a < 3; ++a)
-    for (int b = 0; b < 3; ++b) {
-      double d = 0;
-      for (int k = 0; k < 3; ++k) d += (double)m[a * 4 + k] * (double)m[b * 4 + k];  // columns a and b
-      if (std::fabs(d - (a == b ? 1.0 : 0.0)) > 0.1) return false;
-    }
-  return true;
-}
-
 // blocks of dst per axis that the box of ONE src block can overlap: the box is 9 src voxels wide, its image lies inside the
 // axis-aligned box of |R| * 9 vs_src; + 2 voxels margin (k_merge_enumerate), + 1 for rounding; a range of L voxels meets at most
 // floor(L / 8) + 2 blocks
@@ -72,7 +46,7 @@ int dsr_merge_volume(dsr_engine *dst, dsr_engine *src, const float src_to_dst_m[
   if (dst == src) return fail(DSR_E_ARG, "merge: dst and src are the same engine");
   if (dst->device != src->device) return fail(DSR_E_ARG, "merge: the engines sit on different devices (move one with dsr_snapshot_export / _import)");
   if (dst->s.use_swapping || src->s.use_swapping) return fail(DSR_E_ARG, "merge: engines with use_swapping are not supported");
-  if (!rigid(src_to_dst_m)) return fail(DSR_E_ARG, "merge: src_to_dst is not a rigid transform");
+  if (!rigid_transform(src_to_dst_m)) return fail(DSR_E_ARG, "merge: src_to_dst is not a rigid transform");
   dsr_merge_params prm;
   dsr_merge_default_params(&prm);
   if (params) prm = *params;
@@ -103,7 +77,7 @@ int dsr_merge_volume(dsr_engine *dst, dsr_engine *src, const float src_to_dst_m[
   CHECK_E(src);
   CHECK_E(dst);
 
-  Scratch sc;
+  Scratch sc("merge: out of device memory for the candidate lists");
   unsigned long long *keysA, *keysB, *voxels;
   uint32_t *bucketsA, *bucketsB;
   int32_t *info, *exc, *excRank, *consumes, *blockRank, *res, *nUnique;

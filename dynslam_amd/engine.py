@@ -791,6 +791,52 @@ class EngineCore:
             raise
         return out
 
+    # ---- aligning another volume to this one (include/dsr_align.h; builder-defined)
+    def _align_api(self):
+        if not hasattr(self, "_aapi"):
+            self._aapi = _capi.bind_align(self.api.lib, self.api.prefix)
+        if self._aapi is None:
+            raise DsrError(_capi.DSR_E_ARG, f"this backend ({self.api.prefix}*) has no include/dsr_align.h entry points")
+        return self._aapi
+
+    def align_from(self, src, init_src_to_dst, log_capacity=None, **params):
+        """Refine init_src_to_dst (4x4, metres of src's world -> metres of this engine's world, row-major numpy) by SDF-to-SDF
+        registration of the volume of engine `src` against this one (dsr_align_volume); neither engine is changed.  params: the
+        fields of dsr_align_params — no_levels, stride and iterations (sequences, coarse first; no_levels defaults to their
+        length), min_w_depth, min_valid_points, termination_threshold, max_residual_m.  Returns a dict: "src_to_dst" (4x4,
+        row-major), the result fields, "log_count" and "log" (a list of dicts, at most log_capacity of them: default all)."""
+        m = np.ascontiguousarray(np.asarray(init_src_to_dst, np.float32).reshape(4, 4).T)  # column-major at the boundary
+        api = self._align_api()
+        prm = _capi.AlignParams()
+        api.align_default_params(C.byref(prm))
+        for key in ("stride", "iterations"):
+            if key in params:
+                seq = [int(v) for v in params.pop(key)]
+                if len(seq) > _capi.ALIGN_MAX_LEVELS:
+                    raise DsrError(_capi.DSR_E_ARG, f"align_from: more than {_capi.ALIGN_MAX_LEVELS} levels")
+                params.setdefault("no_levels", len(seq))
+                for i, v in enumerate(seq):
+                    getattr(prm, key)[i] = v
+        for key, value in params.items():
+            if key not in ("no_levels", "min_w_depth", "min_valid_points", "termination_threshold", "max_residual_m"):
+                raise TypeError(f"align_from: unknown parameter {key}")
+            setattr(prm, key, value)
+        cap = sum(max(int(prm.iterations[i]), 0) for i in range(max(0, min(int(prm.no_levels), _capi.ALIGN_MAX_LEVELS))))
+        cap = cap if log_capacity is None else int(log_capacity)
+        log = (_capi.AlignLogEntry * max(cap, 1))()
+        res, count = _capi.AlignResult(), C.c_int32(0)
+        self._check(api.align_volume(self._h, src._h, m.ctypes.data_as(C.POINTER(C.c_float)), C.byref(prm), C.byref(res),
+                                     log if cap > 0 else None, cap, C.byref(count)))
+        out = {k: int(getattr(res, k)) for k in ("evaluations", "valid_points", "accepted_any", "converged")}
+        out["f"] = np.float32(res.f)
+        out["src_to_dst"] = np.array(res.src_to_dst_m, np.float32).reshape(4, 4).T.copy()
+        out["log_count"] = count.value
+        out["log"] = [dict(level=g.level, iteration=g.iteration, valid_points=g.valid_points, accepted=g.accepted, f=np.float32(g.f),
+                           lambda_=np.float32(g.lambda_), step=np.array(g.step, np.float32),
+                           src_to_dst=np.array(g.src_to_dst_m, np.float32).reshape(4, 4).T.copy())
+                      for g in log[:min(cap, count.value)]]
+        return out
+
     def profile_reset(self):
         self._check(self.api.profile_reset(self._h))
 
@@ -1013,6 +1059,12 @@ class InfiniTamDriver:
         the rigid transform src_to_dst (other's world -> this world) — what a host calls before it frees a pruned track's
         reconstruction.  Returns the merge result as a dict."""
         return self.core.merge_from(other.core, src_to_dst)
+
+    def AlignFrom(self, other, init_src_to_dst, **params):
+        """ITMMainEngine::AlignFrom (builder-defined, include/dsr_align.h): the transform other's world -> this world, refined from
+        init_src_to_dst by SDF-to-SDF registration of the two volumes — what a host calls before MergeFrom, whose pose argument
+        it produces (INTEGRATION.md "align, then merge").  Returns EngineCore.align_from's dict."""
+        return self.core.align_from(other.core, init_src_to_dst, **params)
 
     def SaveToFile(self, path):
         """ITMMainEngine::SaveToFile of InfiniTAM v3 (builder-defined here: the reference's fork has no checkpoint): the volume's

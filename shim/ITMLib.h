@@ -28,6 +28,7 @@
 #include "../include/dsr_snapshot.h"
 #include "../include/dsr_mesh.h"
 #include "../include/dsr_merge.h"
+#include "../include/dsr_align.h"
 
 // The tracker's entry points are referenced WEAKLY: a host linked against a library without them (the CPU oracle's orc_* build
 // of the reference's hosts) still links, and ITMTrackingController::Track then throws as it did before the tracker existed.
@@ -49,6 +50,9 @@ int dsr_save_scene_to_mesh_coloured(dsr_engine *e, const char *path, int complet
 // ... and the volume merge's (include/dsr_merge.h): MergeFrom throws on a library without it
 int dsr_merge_volume(dsr_engine *dst, dsr_engine *src, const float src_to_dst_m[16], const dsr_merge_params *params,
                      dsr_merge_result *result) __attribute__((weak));
+// ... and the volume alignment's (include/dsr_align.h): AlignFrom throws on a library without it
+int dsr_align_volume(dsr_engine *dst, dsr_engine *src, const float init_src_to_dst_m[16], const dsr_align_params *params,
+                     dsr_align_result *result, dsr_align_log_entry *log, int32_t log_capacity, int32_t *log_count) __attribute__((weak));
 }
 
 #ifndef SDF_BLOCK_SIZE
@@ -640,6 +644,16 @@ class ITMMainEngine {
     dsr_merge_result res;
     memset(&res, 0, sizeof res);
     ITMLib::Engine::dsr_throw(dsr_merge_volume(engine_, other.engine_, src_to_dst.m, nullptr, &res));
+    return res;
+  }
+  // BUILDER-DEFINED (include/dsr_align.h): the transform other's world -> this one's, refined from `init` by
+  // SDF-to-SDF registration of the two volumes (both are left as they are) — the pose MergeFrom needs (INTEGRATION.md "align, then
+  // merge").  The result holds the refined transform (column-major), or `init` when no evaluation was accepted.
+  dsr_align_result AlignFrom(ITMMainEngine &other, const Matrix4f &init, const dsr_align_params *params = nullptr) {
+    if (!dsr_align_volume) throw std::runtime_error("this library has no volume alignment (include/dsr_align.h)");
+    dsr_align_result res;
+    memset(&res, 0, sizeof res);
+    ITMLib::Engine::dsr_throw(dsr_align_volume(engine_, other.engine_, init.m, params, &res, nullptr, 0, nullptr));
     return res;
   }
   // ITMMainEngine::SaveToFile / LoadFromFile: the names of InfiniTAM v3, BUILDER-DEFINED here (the reference's fork of v2 has no
