@@ -430,6 +430,8 @@ def bind_snapshot(lib, prefix):
 
 # ---- include/dsr_mesh.h: the complete mesh of a swapping engine.  A table of its own, like the snapshot's (the oracle has none).
 MESH_ABI_VERSION = 2  # == DSR_MESH_ABI_VERSION
+MESH_INDEXED_ABI_VERSION = 1  # == DSR_MESH_INDEXED_ABI_VERSION
+MESH_COMPLETE, MESH_COLOURS, MESH_NORMALS = 1, 2, 4  # DSR_MESH_* flags of dsr_mesh_scene_indexed
 
 MESH_SIGNATURES = {
     "mesh_abi_version": (C.c_int32, []),
@@ -442,6 +444,17 @@ MESH_SIGNATURES = {
     "mesh_write_obj_coloured": (C.c_int, [_H, C.c_char_p]),
     "mesh_write_ply": (C.c_int, [_H, C.c_char_p]),
     "save_scene_to_mesh_coloured": (C.c_int, [_H, C.c_char_p, C.c_int]),
+    # indexed meshes (a version of their own: MESH_INDEXED_ABI_VERSION)
+    "mesh_indexed_abi_version": (C.c_int32, []),
+    "mesh_scene_indexed": (C.c_int, [_H, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "mesh_indexed_get_vertices": (C.c_int, [_H, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "mesh_indexed_get_normals": (C.c_int, [_H, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "mesh_indexed_get_colours": (C.c_int, [_H, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "mesh_indexed_get_indices": (C.c_int, [_H, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "mesh_indexed_free": (C.c_int, [_H]),
+    "mesh_indexed_write_ply": (C.c_int, [_H, C.c_char_p]),
+    "mesh_indexed_write_obj": (C.c_int, [_H, C.c_char_p]),
+    "save_scene_to_mesh_indexed": (C.c_int, [_H, C.c_char_p, C.c_int]),
 }
 
 
@@ -457,6 +470,8 @@ def bind_mesh(lib, prefix):
         setattr(ns, name, fn)
     if ns.mesh_abi_version() != MESH_ABI_VERSION:
         raise ImportError("complete mesher ABI version mismatch (include/dsr_mesh.h)")
+    if ns.mesh_indexed_abi_version() != MESH_INDEXED_ABI_VERSION:
+        raise ImportError("indexed mesher ABI version mismatch (include/dsr_mesh.h)")
     return ns
 
 

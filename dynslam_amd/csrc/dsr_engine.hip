@@ -20,6 +20,7 @@ using namespace dsr_internal;
 #include "k_swap.h"
 #include "k_mesh.h"
 #include "k_mesh_complete.h"
+#include "k_mesh_indexed.h"
 #include "k_small.h"
 #include "k_batch.h"
 #include "k_batch_gc.h"
@@ -163,7 +164,7 @@ void free_all(dsr_engine *e) {
     F(rs->visibleIDs); F(rs->visibleIDsAlt); F(rs->visBlocks); F(rs->visBlocksAlt); F(rs->visType); F(rs->minmax); F(rs->raycastResult); F(rs->raycastImage); F(rs->rayBox);
   }
   dsr_internal::tracker_free(e);
-  F(e->tileSums); F(e->integrateStats); F(e->allocList); F(e->allocWork); F(e->meshTris); F(e->meshClr); F(e->rgb); F(e->depth); F(e->depthTmp); F(e->rawDepth); F(e->pointsMap); F(e->normalsMap);
+  F(e->tileSums); F(e->integrateStats); F(e->allocList); F(e->allocWork); F(e->meshTris); F(e->meshClr); F(e->imesh.verts); F(e->imesh.normals); F(e->imesh.colours); F(e->imesh.indices); F(e->rgb); F(e->depth); F(e->depthTmp); F(e->rawDepth); F(e->pointsMap); F(e->normalsMap);
   F(e->freeDepth); F(e->aosScratch);
   F(e->fifoPlanes); F(e->decayCand); F(e->decayFlags);
   if (e->maskHost) (void)hipHostFree(e->maskHost);
@@ -2082,6 +2083,166 @@ int dsr_save_scene_to_mesh_coloured(dsr_engine *e, const char *path, int complet
   if (st == DSR_OK) st = ends_in_ply(path) ? dsr_mesh_write_ply(e, path) : dsr_mesh_write_obj_coloured(e, path);
   if (e) (void)mesh_release(e);
   return st;
+}
+
+// ---- indexed meshes (include/dsr_mesh.h, k_mesh_indexed.h; builder-defined).  The launches; the entry points
+// are dsr_mesh_indexed.hip's.
+
+extern "C++" {
+namespace {
+// Count per block (used edges, triangles), two scans, ONE read-back of both totals, exact buffers, then per chunk the vertex and the
+// index pass.  prep as in mesh_from_list, with pool planes for the 27 blocks a lattice touches.  Into e->imesh (released by the caller).
+template <class SRC, bool COLOUR, class PREP>
+int mesh_indexed_from_list(dsr_engine *e, const SceneP &sc, const int32_t *list, const int32_t *nPtr, int n, int2 *tileSums, int chunk,
+                           bool normals, PREP prep) {
+  MeshScratch scratch;
+  uint32_t *vCount = nullptr, *tCount = nullptr, *vBase = nullptr, *tBase = nullptr;
+  uint2 *laneInfo = nullptr;
+  int32_t *posOf = nullptr, *totals = nullptr;
+  int st;
+  if ((st = scratch.get(&vCount, (size_t)n)) || (st = scratch.get(&tCount, (size_t)n)) || (st = scratch.get(&vBase, (size_t)n)) ||
+      (st = scratch.get(&tBase, (size_t)n)) || (st = scratch.get(&laneInfo, (size_t)n * 64)) || (st = scratch.get(&posOf, (size_t)e->E)) ||
+      (st = scratch.get(&totals, (size_t)2 * CTR_COUNT)))
+    return st;
+  MeshP mp; mp.voxelSize = e->s.voxel_size; mp.hashMask = (uint32_t)(e->noBuckets - 1); mp.noBuckets = e->noBuckets;
+  const int tiles = div_up(n, kTile);
+  const bool oneChunk = n <= chunk;
+  auto grid = [](int items) { return dim3(std::min(8192, div_up(items, kMeshWaves))); };
+  SRC src{};
+  for (int first = 0; first < n; first += chunk) {
+    const int end = (int)std::min<long long>((long long)first + chunk, n);
+    if ((st = prep(first, end, src))) return st;
+    LAUNCH(e, "mesh_indexed_count", (k_mesh_indexed_count<SRC>), grid(end - first), dim3(64 * kMeshWaves), sc, mp, list, nPtr, laneInfo,
+           vCount, tCount, src);
+  }
+  // (the scans leave their totals in CTR_MESH_TOTAL of the counters they are given: two sets of this call's own)
+  HIP_TRY(hipMemsetAsync(totals, 0, 2 * CTR_COUNT * 4, e->stream));
+  for (int k = 0; k < 2; ++k) {
+    SceneP scK = sc;
+    scK.ctr = totals + k * CTR_COUNT;
+    const uint32_t *count = k ? tCount : vCount;
+    LAUNCH(e, "mesh_scan", k_u32_tile_sums, dim3(tiles), dim3(kTileThreads), count, nPtr, tileSums);
+    LAUNCH(e, "scan_tiles", k_scan_tile_sums, dim3(1), dim3(1024), tileSums, tiles, scK, (int)SCAN_MESH, 0);
+    LAUNCH(e, "mesh_scan", k_u32_tile_offsets, dim3(tiles), dim3(kTileThreads), count, nPtr, (const int2 *)tileSums, k ? tBase : vBase);
+  }
+  HIP_TRY(hipMemsetAsync(posOf, 0xff, (size_t)e->E * 4, e->stream));
+  LAUNCH(e, "mesh_indexed_positions", k_mesh_list_positions, dim3(std::min(1024, div_up(n, 256))), dim3(256), list, nPtr, posOf);
+  int32_t host[2 * CTR_COUNT];
+  HIP_TRY(hipMemcpyAsync(host, totals, sizeof host, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const int nv = host[CTR_MESH_TOTAL], nt = host[CTR_COUNT + CTR_MESH_TOTAL];
+  if (nv < 0 || nt < 0) return fail(DSR_E_ARG, "indexed mesh has more than 2^31 - 1 vertices or triangles");
+  dsr_engine::IndexedMesh &m = e->imesh;
+  auto alloc = [&](auto **p, size_t count) {
+    return count == 0 || hipMalloc(reinterpret_cast<void **>(p), count * 4) == hipSuccess;
+  };
+  if (!alloc(&m.verts, (size_t)nv * 3) || !alloc(&m.indices, (size_t)nt * 3) || (normals && !alloc(&m.normals, (size_t)nv * 3)) ||
+      (COLOUR && !alloc(&m.colours, (size_t)nv))) {
+    (void)hipGetLastError();
+    return fail(DSR_E_NOMEM, "indexed mesh buffer allocation failed");
+  }
+  if (nv > 0 || nt > 0) {
+    for (int first = 0; first < n && st == DSR_OK; first += chunk) {
+      const int end = (int)std::min<long long>((long long)first + chunk, n);
+      if (!oneChunk && (st = prep(first, end, src))) break;
+      LAUNCH(e, "mesh_indexed_vertices", (k_mesh_indexed_vertices<SRC, COLOUR>), grid(end - first), dim3(64 * kMeshWaves), sc, mp, list,
+             nPtr, (const uint2 *)laneInfo, (const uint32_t *)vBase, m.verts, m.normals, m.colours, (unsigned long long)nv, src);
+      LAUNCH(e, "mesh_indexed_indices", (k_mesh_indexed_indices<SRC>), grid(end - first), dim3(64 * kMeshWaves), sc, mp, list, nPtr,
+             (const uint2 *)laneInfo, (const uint32_t *)vBase, (const uint32_t *)tBase, (const int32_t *)posOf, m.indices,
+             (unsigned long long)nt, src);
+    }
+  }
+  const hipError_t err = hipStreamSynchronize(e->stream);  // (also before the scratch goes)
+  if (st == DSR_OK && err != hipSuccess) st = fail(DSR_E_DEVICE, hipGetErrorString(err));
+  if (st == DSR_OK) { m.nVerts = (uint64_t)nv; m.nTris = (uint64_t)nt; }
+  return st;
+}
+template <class SRC> int no_prep_any(int, int, SRC &) { return DSR_OK; }
+}  // namespace
+}  // extern "C++"
+
+extern "C++" int dsr_internal::engine_mesh_indexed_release(dsr_engine *e) {
+  dsr_engine::IndexedMesh &m = e->imesh;
+  if (m.verts || m.normals || m.colours || m.indices) HIP_TRY(hipStreamSynchronize(e->stream));
+  for (void *p : {(void *)m.verts, (void *)m.normals, (void *)m.colours, (void *)m.indices})
+    if (p) (void)hipFree(p);
+  m = dsr_engine::IndexedMesh{};
+  return DSR_OK;
+}
+
+// Everything this call writes is its own, with and without DSR_MESH_COMPLETE: the list, the tile sums, the counters the scans use.
+extern "C++" int dsr_internal::engine_mesh_indexed(dsr_engine *e, int flags) {
+  int st = engine_mesh_indexed_release(e);
+  if (st) return st;
+  const bool complete = (flags & DSR_MESH_COMPLETE) != 0, colours = (flags & DSR_MESH_COLOURS) != 0, normals = (flags & DSR_MESH_NORMALS) != 0;
+  MeshScratch scratch;
+  SceneP sc = e->scene;
+  int2 *tileSums = nullptr;
+  int32_t *list = nullptr;
+  if ((st = scratch.get(&sc.ctr, (size_t)CTR_COUNT)) || (st = scratch.get(&tileSums, (size_t)e->numTilesE)) ||
+      (st = scratch.get(&list, (size_t)e->E)))
+    return st;
+  HIP_TRY(hipMemsetAsync(sc.ctr, 0, CTR_COUNT * 4, e->stream));
+  if (complete) LAUNCH(e, "mesh_candidates", k_owning_count, dim3(e->numTilesE), dim3(kTileThreads), sc, e->E, tileSums);
+  else LAUNCH(e, "mesh_candidates", k_allocated_count, dim3(e->numTilesE), dim3(kTileThreads), sc, e->E, tileSums);
+  LAUNCH(e, "scan_tiles", k_scan_tile_sums, dim3(1), dim3(1024), tileSums, e->numTilesE, sc, (int)SCAN_NCAND, e->E);
+  if (complete) LAUNCH(e, "mesh_candidates", k_owning_write, dim3(e->numTilesE), dim3(kTileThreads), sc, e->E, (const int2 *)tileSums, list, e->E);
+  else LAUNCH(e, "mesh_candidates", k_allocated_write, dim3(e->numTilesE), dim3(kTileThreads), sc, e->E, (const int2 *)tileSums, list, e->E);
+  const int32_t *nPtr = sc.ctr + CTR_DECAY_NCAND;
+  int32_t head[2] = {0, 0};  // list length; host slots handed out (an upper bound of the stored entries)
+  HIP_TRY(hipMemcpyAsync(&head[0], nPtr, 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(&head[1], e->scene.ctr + CTR_HOST_USED, 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const int n = head[0];
+  dsr_engine::IndexedMesh &m = e->imesh;
+  if (n > 0) {
+    if (!complete || !e->scene.swapStored) {
+      st = colours ? mesh_indexed_from_list<MeshResident, true>(e, sc, list, nPtr, n, tileSums, n, normals, no_prep_any<MeshResident>)
+                   : mesh_indexed_from_list<MeshResident, false>(e, sc, list, nPtr, n, tileSums, n, normals, no_prep_any<MeshResident>);
+    } else {
+      if (head[1] < 0 || head[1] > host_store_slots(e)) return fail(DSR_E_DEVICE, "host store inconsistent");
+      // The pool, as mesh_complete's — but the lattice of a listed entry now touches 27 blocks.  The pool is sized by the DISTINCT
+      // planes a chunk can need: never more than the store holds, and never more than 27 per listed entry.
+      const size_t slotBytes = colours ? kColourSlotBytes : kPlaneBytes;
+      int chunk = (1 << 17) / (int)(slotBytes / kPlaneBytes);
+      if (const char *c = getenv("DSR_MESH_CHUNK")) chunk = std::max(1, atoi(c));
+      if (head[1] <= 8ll * chunk) chunk = std::max(chunk, n);
+      const int poolCap = (int)std::min<long long>(head[1], 27ll * std::min(chunk, n));
+      int32_t *planeOf = nullptr, *poolIds = nullptr, *poolCtr = nullptr;
+      uint8_t *pool = nullptr;
+      if ((st = scratch.get(&planeOf, (size_t)e->E)) || (st = scratch.get(&poolIds, (size_t)poolCap)) ||
+          (st = scratch.get(&poolCtr, 2)) || (st = scratch.get(&pool, (size_t)poolCap * slotBytes)))
+        return st;
+      MeshP mp; mp.voxelSize = e->s.voxel_size; mp.hashMask = (uint32_t)(e->noBuckets - 1); mp.noBuckets = e->noBuckets;
+      const int noSlots = (int)std::min<long long>(host_store_slots(e), 0x7fffffff);
+      HIP_TRY(hipMemsetAsync(poolCtr, 0, 8, e->stream));
+      auto prep = [&](int first, int end, auto &src) -> int {
+        src.planeOf = planeOf; src.pool = pool; src.firstItem = first; src.endItem = end;
+        HIP_TRY(hipMemsetAsync(planeOf, 0xff, (size_t)e->E * 4, e->stream));
+        HIP_TRY(hipMemsetAsync(poolCtr, 0, 4, e->stream));
+        LAUNCH(e, "mesh_mark", k_mesh_mark27, dim3(div_up((long long)(end - first) * 27, 256)), dim3(256), sc, mp, (const int32_t *)list,
+               nPtr, first, end, planeOf, poolIds, poolCap, poolCtr);
+        if (colours)
+          LAUNCH(e, "mesh_gather", (k_mesh_gather<true>), dim3(std::max(1, std::min(1024, div_up(poolCap, 4)))), dim3(256), sc,
+                 (int)e->s.max_w, e->noBlocks, noSlots, (const int32_t *)poolIds, (const int32_t *)poolCtr, poolCap, pool);
+        else
+          LAUNCH(e, "mesh_gather", (k_mesh_gather<false>), dim3(std::max(1, std::min(1024, div_up(poolCap, 4)))), dim3(256), sc,
+                 (int)e->s.max_w, e->noBlocks, noSlots, (const int32_t *)poolIds, (const int32_t *)poolCtr, poolCap, pool);
+        return DSR_OK;
+      };
+      st = colours ? mesh_indexed_from_list<MeshPooledColour, true>(e, sc, list, nPtr, n, tileSums, chunk, normals, prep)
+                   : mesh_indexed_from_list<MeshPooled, false>(e, sc, list, nPtr, n, tileSums, chunk, normals, prep);
+      if (st == DSR_OK) {
+        int32_t over = 0;
+        HIP_TRY(hipMemcpy(&over, poolCtr + 1, 4, hipMemcpyDeviceToHost));
+        if (over) st = fail(DSR_E_DEVICE, "mesh plane pool overflow");
+      }
+    }
+  }
+  if (st != DSR_OK) { (void)engine_mesh_indexed_release(e); return st; }
+  m.flags = flags;
+  m.valid = true;
+  return DSR_OK;
 }
 
 #ifdef DSR_RAYCAST_STATS

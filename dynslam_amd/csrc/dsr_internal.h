@@ -10,6 +10,8 @@
 //   dsr_snapshot.hip  save / load / export / import of an engine's complete state (include/dsr_snapshot.h): the file format, pack / unpack
 //   dsr_merge.hip     folding one volume into another at a rigid pose (include/dsr_merge.h): candidates, ordered insert, the pull
 //   dsr_align.hip     aligning one volume to another, SDF to SDF (include/dsr_align.h): the list of blocks, the queued evaluations
+//   dsr_mesh_indexed.hip  the indexed mesh's entry points (include/dsr_mesh.h): flags, getters, the PLY / OBJ writers.  Host code only:
+//                     its kernels (k_mesh_indexed.h) build on the mesher's policies and scans, so dsr_engine.hip holds their launches
 // Every kernel header (k_*.h) is included by exactly ONE of them: kernels have external linkage.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -139,6 +141,14 @@ struct dsr_engine {
   dsr_triangle_colour *meshClr = nullptr;  // its vertex colours (dsr_mesh_scene_coloured), else null
   bool meshColoured = false;  // the current mesh was made by dsr_mesh_scene_coloured (meshClr is null when it has no triangles)
   uint64_t meshCount = 0;
+  // the indexed mesh (dsr_mesh_scene_indexed, include/dsr_mesh.h): a slot of its own — the soup mesh above neither replaces nor frees it
+  struct IndexedMesh {
+    float *verts = nullptr, *normals = nullptr;       // 3 floats per vertex; normals null without DSR_MESH_NORMALS
+    uint32_t *colours = nullptr, *indices = nullptr;  // an (r, g, b, alpha) word per vertex, null without DSR_MESH_COLOURS; 3 per triangle
+    uint64_t nVerts = 0, nTris = 0;
+    int flags = 0;
+    bool valid = false;  // a mesh has been made (it may have no vertices)
+  } imesh;
 
   // view
   bool hasView = false;
@@ -348,6 +358,10 @@ int engine_small_bit_words();
 bool engine_in_live_batch(dsr_engine *e);
 int engine_render(dsr_engine *e, int type, const float pose_m[16], const float intrinsics[4], void *rgba_out, void *depth_out,
                   bool outIsDevice);
+// ... for dsr_mesh_indexed.hip: build the indexed mesh into e->imesh (flags checked by the caller; any earlier one is released
+// first), release it
+int engine_mesh_indexed(dsr_engine *e, int flags);
+int engine_mesh_indexed_release(dsr_engine *e);
 // dsr_hostio.hip: is [p, p + bytes) inside a range the caller page-locked through dsr_pin_host_buffer?
 bool host_range_pinned(const void *p, size_t bytes);
 // dsr_profile.hip: div_short(x, b) == x / b for every x? (k_integrate.h; checked once per engine for its mu)

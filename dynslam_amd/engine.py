@@ -758,6 +758,50 @@ class EngineCore:
         """Coloured mesh, written as PLY when the path ends in .ply, else as a coloured OBJ; the mesh is freed."""
         self._check(self._mesh_api().save_scene_to_mesh_coloured(self._h, str(path).encode(), int(bool(complete))))
 
+    # ---- indexed meshes (include/dsr_mesh.h, DESIGN.md §11.3; builder-defined)
+    @staticmethod
+    def _indexed_flags(complete, colours, normals):
+        return (_capi.MESH_COMPLETE if complete else 0) | (_capi.MESH_COLOURS if colours else 0) | (_capi.MESH_NORMALS if normals else 0)
+
+    def mesh_scene_indexed(self, complete=False, colours=False, normals=True):
+        """The map's mesh as welded vertices + indices (dsr_mesh_scene_indexed): one vertex per lattice edge, no triangle cap.
+        Returns (vertices float32 [m, 3] in metres, indices uint32 [n, 3], normals float32 [m, 3] or None, RGBA uint8 [m, 4] or
+        None).  The mesh stays in a slot of its own (mesh_indexed_write_ply / _obj / mesh_indexed_free); the soup mesh of
+        mesh_scene and its kin is not touched."""
+        m, nv, nt = self._mesh_api(), C.c_uint64(0), C.c_uint64(0)
+        self._check(m.mesh_scene_indexed(self._h, self._indexed_flags(complete, colours, normals), C.byref(nv), C.byref(nt)))
+        verts = np.empty((nv.value, 3), np.float32)
+        idx = np.empty((nt.value, 3), np.uint32)
+        self._check(m.mesh_indexed_get_vertices(self._h, verts.ctypes.data_as(C.c_void_p), 0, nv.value))
+        self._check(m.mesh_indexed_get_indices(self._h, idx.ctypes.data_as(C.c_void_p), 0, nt.value))
+        return verts, idx, (self.mesh_indexed_get_normals(0, nv.value) if normals else None), \
+            (self.mesh_indexed_get_colours(0, nv.value) if colours else None)
+
+    def mesh_indexed_get_normals(self, first, count):
+        """float32 [count, 3] of the indexed mesh; raises when it was made without normals."""
+        out = np.empty((int(count), 3), np.float32)
+        self._check(self._mesh_api().mesh_indexed_get_normals(self._h, out.ctypes.data_as(C.c_void_p), int(first), int(count)))
+        return out
+
+    def mesh_indexed_get_colours(self, first, count):
+        """RGBA uint8 [count, 4] of the indexed mesh; raises when it was made without colours."""
+        out = np.empty((int(count), 4), np.uint8)
+        self._check(self._mesh_api().mesh_indexed_get_colours(self._h, out.ctypes.data_as(C.c_void_p), int(first), int(count)))
+        return out
+
+    def mesh_indexed_write_ply(self, path):
+        self._check(self._mesh_api().mesh_indexed_write_ply(self._h, str(path).encode()))
+
+    def mesh_indexed_write_obj(self, path):
+        self._check(self._mesh_api().mesh_indexed_write_obj(self._h, str(path).encode()))
+
+    def mesh_indexed_free(self):
+        self._check(self._mesh_api().mesh_indexed_free(self._h))
+
+    def save_scene_to_mesh_indexed(self, path, complete=False, colours=False, normals=True):
+        """Indexed mesh, written as PLY when the path ends in .ply, else as OBJ; the indexed mesh is freed."""
+        self._check(self._mesh_api().save_scene_to_mesh_indexed(self._h, str(path).encode(), self._indexed_flags(complete, colours, normals)))
+
     def dump_merged_block(self, entry):
         """For tests: the block of a table entry as the complete mesher sees it (dsr_dump_merged_block), None if it owns no data."""
         out = np.empty(BLOCK_SIZE3, VOXEL_DTYPE)
@@ -1042,12 +1086,15 @@ class InfiniTamDriver:
     def Reset(self):
         self.core.reset_scene()
 
-    def SaveSceneToMesh(self, path, complete=False, coloured=False):
+    def SaveSceneToMesh(self, path, complete=False, coloured=False, indexed=False):
         """ITMMainEngine::SaveSceneToMesh as called by DynSlam::SaveStaticMap (DynSlam.cpp:188-196)
         and, per instance, InstanceReconstructor::SaveObjectToMesh (InstanceReconstructor.cpp:736-763).
         complete=True (builder-defined, include/dsr_mesh.h): the whole map of a swapping engine, host-store blocks included.
-        coloured=True (builder-defined): per-vertex colour; a PLY when the path ends in .ply, else an OBJ with "v x y z r g b"."""
-        if coloured:
+        coloured=True (builder-defined): per-vertex colour; a PLY when the path ends in .ply, else an OBJ with "v x y z r g b".
+        indexed=True (builder-defined): welded vertices with normals + indices, no triangle cap; PLY or OBJ by the extension."""
+        if indexed:
+            self.core.save_scene_to_mesh_indexed(path, complete=complete, colours=coloured, normals=True)
+        elif coloured:
             self.core.save_scene_to_mesh_coloured(path, complete)
         elif complete:
             self.core.save_scene_to_mesh_complete(path)

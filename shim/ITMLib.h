@@ -47,6 +47,9 @@ int dsr_mesh_get_colours(dsr_engine *e, dsr_triangle_colour *out, uint64_t first
 int dsr_mesh_write_obj_coloured(dsr_engine *e, const char *path) __attribute__((weak));
 int dsr_mesh_write_ply(dsr_engine *e, const char *path) __attribute__((weak));
 int dsr_save_scene_to_mesh_coloured(dsr_engine *e, const char *path, int complete) __attribute__((weak));
+// ... and the indexed meshes' (DSR_MESH_INDEXED_ABI_VERSION 1): SaveIndexedSceneToMesh throws on a library without them
+int dsr_mesh_scene_indexed(dsr_engine *e, int flags, uint64_t *n_vertices, uint64_t *n_triangles) __attribute__((weak));
+int dsr_save_scene_to_mesh_indexed(dsr_engine *e, const char *path, int flags) __attribute__((weak));
 // ... and the volume merge's (include/dsr_merge.h): MergeFrom throws on a library without it
 int dsr_merge_volume(dsr_engine *dst, dsr_engine *src, const float src_to_dst_m[16], const dsr_merge_params *params,
                      dsr_merge_result *result) __attribute__((weak));
@@ -635,6 +638,14 @@ class ITMMainEngine {
   void SaveColouredSceneToMesh(const char *fileName, bool complete = false) {
     if (!dsr_save_scene_to_mesh_coloured) throw std::runtime_error("this library has no coloured mesher (include/dsr_mesh.h)");
     ITMLib::Engine::dsr_throw(dsr_save_scene_to_mesh_coloured(engine_, fileName, complete ? 1 : 0));
+  }
+  // BUILDER-DEFINED (include/dsr_mesh.h): the mesh as welded vertices with normals + indices, one vertex per lattice
+  // edge and no triangle cap; a binary PLY when the name ends in ".ply", else an OBJ with vn lines.  complete: as
+  // SaveCompleteSceneToMesh; coloured: per-vertex colour as SaveColouredSceneToMesh.
+  void SaveIndexedSceneToMesh(const char *fileName, bool complete = false, bool coloured = false) {
+    if (!dsr_save_scene_to_mesh_indexed) throw std::runtime_error("this library has no indexed mesher (include/dsr_mesh.h)");
+    ITMLib::Engine::dsr_throw(dsr_save_scene_to_mesh_indexed(engine_, fileName, (complete ? DSR_MESH_COMPLETE : 0) |
+                                                                                    (coloured ? DSR_MESH_COLOURS : 0) | DSR_MESH_NORMALS));
   }
   // BUILDER-DEFINED (include/dsr_merge.h): the volume of `other` resampled into this one at the rigid transform
   // src_to_dst (metres of other's world -> metres of this one's), allocating what this volume lacks — what a host calls before it
