@@ -556,3 +556,47 @@ def bind_align(lib, prefix):
     if ns.align_abi_version() != ALIGN_ABI_VERSION:
         raise ImportError("align ABI version mismatch (include/dsr_align.h)")
     return ns
+
+
+# ---- include/dsr_dense.h: a volume resampled into a dense grid and back.  A table of its own, like the merge's (the oracle has none).
+DENSE_ABI_VERSION = 1  # == DSR_DENSE_ABI_VERSION
+DENSE_NEAREST, DENSE_TRILINEAR = 0, 1  # DSR_DENSE_NEAREST / _TRILINEAR
+DENSE_REPLACE, DENSE_COMBINE = 0, 1    # DSR_DENSE_REPLACE / _COMBINE
+
+
+class DenseGrid(C.Structure):  # struct dsr_dense_grid
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("pitch", C.c_float), ("mu", C.c_float),
+                ("grid_to_world_m", C.c_float * 16), ("sampling", C.c_int32), ("min_w_depth", C.c_int32), ("import_mode", C.c_int32),
+                ("fill_w", C.c_int32), ("reserved", C.c_int32 * 8)]
+
+
+class DenseResult(C.Structure):  # struct dsr_dense_result
+    _fields_ = [("points_with_data", C.c_int64), ("candidate_blocks", C.c_int32), ("blocks_with_data", C.c_int32),
+                ("blocks_allocated", C.c_int32), ("blocks_dropped", C.c_int32), ("voxels_updated", C.c_int64), ("reserved", C.c_int32 * 4)]
+
+
+assert C.sizeof(DenseGrid) == 132 and C.sizeof(DenseResult) == 48
+
+DENSE_SIGNATURES = {
+    "dense_abi_version": (C.c_int32, []),
+    "dense_default_grid": (None, [C.POINTER(DenseGrid)]),
+    "dense_export": (C.c_int, [_H, C.POINTER(DenseGrid), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DenseResult)]),
+    "dense_export_dev": (C.c_int, [_H, C.POINTER(DenseGrid), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DenseResult)]),
+    "dense_import": (C.c_int, [_H, C.POINTER(DenseGrid), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DenseResult)]),
+    "dense_import_dev": (C.c_int, [_H, C.POINTER(DenseGrid), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DenseResult)]),
+}
+
+
+def bind_dense(lib, prefix):
+    """The dense-grid entry points `prefix + name` in `lib`, or None when the library has none (the CPU oracle)."""
+    if not hasattr(lib, prefix + "dense_export"):
+        return None
+    ns = SimpleNamespace()
+    for name, (res, args) in DENSE_SIGNATURES.items():
+        fn = getattr(lib, prefix + name)
+        fn.restype = res
+        fn.argtypes = args
+        setattr(ns, name, fn)
+    if ns.dense_abi_version() != DENSE_ABI_VERSION:
+        raise ImportError("dense ABI version mismatch (include/dsr_dense.h)")
+    return ns

@@ -8,7 +8,8 @@
 //   dsr_track.hip     the ICP depth tracker (include/dsr_track.h): its buffers, the launch sequence of one dsr_track, the read-back
 //   dsr_eval.hip      LIDAR-vs-depth accuracy scoring (include/dsr_eval.h): argument checks, the one launch, the read-back
 //   dsr_snapshot.hip  save / load / export / import of an engine's complete state (include/dsr_snapshot.h): the file format, pack / unpack
-//   dsr_merge.hip     folding one volume into another at a rigid pose (include/dsr_merge.h): candidates, ordered insert, the pull
+//   dsr_merge.hip     folding one volume into another at a rigid pose (include/dsr_merge.h): candidates, ordered insert, the pull;
+//                     and, on the same device functions and insert, a volume resampled into a dense grid and back (include/dsr_dense.h)
 //   dsr_align.hip     aligning one volume to another, SDF to SDF (include/dsr_align.h): the list of blocks, the queued evaluations
 //   dsr_mesh_indexed.hip  the indexed mesh's entry points (include/dsr_mesh.h): flags, getters, the PLY / OBJ writers.  Host code only:
 //                     its kernels (k_mesh_indexed.h) build on the mesher's policies and scans, so dsr_engine.hip holds their launches

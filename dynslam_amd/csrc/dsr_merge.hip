@@ -1,4 +1,6 @@
-// dsr_merge.hip — include/dsr_merge.h: fold one volume into another at a rigid pose.
+// dsr_merge.hip — include/dsr_merge.h: fold one volume into another at a rigid pose, and include/dsr_dense.h:
+// resample a volume into a dense grid and back (the second half of this file) — the merge with an array on one
+// side, on the merge's device functions and ordered insert.
 //
 // One call = one chain of launches on dst's stream, after an event of src's:
 //   fill + enumerate      the candidate keys of every allocated src entry (k_merge.h);
@@ -15,6 +17,8 @@ using namespace dsr_internal;
 
 #include "dsr_math.h"
 #include "k_merge.h"
+#include "k_dense.h"
+#include "../../include/dsr_dense.h"
 #include "../../include/dsr_merge.h"
 
 namespace {
@@ -25,6 +29,28 @@ namespace {
 int boxes_per_axis(const float *m, int row, double vsSrc, double vsDst) {
   const double ext = (std::fabs((double)m[row]) + std::fabs((double)m[4 + row]) + std::fabs((double)m[8 + row])) * 9.0 * vsSrc / vsDst + 3.0;
   return (int)std::floor(ext / 8.0) + 2;
+}
+
+// The ordered insert of the candidates dst lacks (dsr_merge.h step 3), queued on dst's stream: a stable sort by bucket (the key
+// order survives inside a bucket), plan, two exclusive sums, apply, finish.  bucketsA / keysA: per candidate its bucket
+// (kMergeNoBucket: nothing to insert) and key; the B arrays, plan .. blockRank: N elements of scratch; m: the dst fields.
+int ordered_insert(dsr_engine *dst, const MergeP &m, int N, uint32_t *bucketsA, uint32_t *bucketsB, unsigned long long *keysA,
+                   unsigned long long *keysB, int2 *plan, int32_t *exc, int32_t *excRank, int32_t *consumes, int32_t *blockRank,
+                   int32_t *res, uint8_t *tmp, size_t tmpBytes) {
+  ProfScope ps(dst, "merge_alloc");
+  size_t b = tmpBytes;
+  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, b, bucketsA, bucketsB, keysA, keysB, N, 0, 32, dst->stream));
+  const dim3 g(div_up(N, 256));
+  hipLaunchKernelGGL(k_merge_plan, g, dim3(256), 0, dst->stream, m, dst->scene, (const uint32_t *)bucketsB, N, plan, exc, res);
+  b = tmpBytes; HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, b, exc, excRank, N, dst->stream));
+  hipLaunchKernelGGL(k_merge_consume, g, dim3(256), 0, dst->stream, (const uint32_t *)bucketsB, N, (const int32_t *)exc,
+                     (const int32_t *)excRank, (const int32_t *)res, consumes);
+  b = tmpBytes; HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, b, consumes, blockRank, N, dst->stream));
+  hipLaunchKernelGGL(k_merge_apply, g, dim3(256), 0, dst->stream, m, dst->scene, (const uint32_t *)bucketsB,
+                     (const unsigned long long *)keysB, N, (const int2 *)plan, (const int32_t *)exc, (const int32_t *)excRank,
+                     (const int32_t *)consumes, (const int32_t *)blockRank, dst->live.visType, dst->freeview.visType, res);
+  hipLaunchKernelGGL(k_merge_finish, dim3(1), dim3(64), 0, dst->stream, dst->scene, res);
+  return DSR_OK;
 }
 
 }  // namespace
@@ -119,20 +145,7 @@ int dsr_merge_volume(dsr_engine *dst, dsr_engine *src, const float src_to_dst_m[
   for (int first = 0; first < N; first += chunk)
     LAUNCH(dst, "merge_has_data", k_merge_has_data, dim3(gridChunk), dim3(256), m, src->scene, dst->scene, (const unsigned long long *)keysA,
            (const int32_t *)nUnique, first, chunk, info, bucketsA, res);
-  {
-    ProfScope ps(dst, "merge_alloc");
-    b = tmpBytes; HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, b, bucketsA, bucketsB, keysA, keysB, N, 0, 32, dst->stream));
-    const dim3 g(div_up(N, 256));
-    hipLaunchKernelGGL(k_merge_plan, g, dim3(256), 0, dst->stream, m, dst->scene, (const uint32_t *)bucketsB, N, plan, exc, res);
-    b = tmpBytes; HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, b, exc, excRank, N, dst->stream));
-    hipLaunchKernelGGL(k_merge_consume, g, dim3(256), 0, dst->stream, (const uint32_t *)bucketsB, N, (const int32_t *)exc,
-                       (const int32_t *)excRank, (const int32_t *)res, consumes);
-    b = tmpBytes; HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, b, consumes, blockRank, N, dst->stream));
-    hipLaunchKernelGGL(k_merge_apply, g, dim3(256), 0, dst->stream, m, dst->scene, (const uint32_t *)bucketsB,
-                       (const unsigned long long *)keysB, N, (const int2 *)plan, (const int32_t *)exc, (const int32_t *)excRank,
-                       (const int32_t *)consumes, (const int32_t *)blockRank, dst->live.visType, dst->freeview.visType, res);
-    hipLaunchKernelGGL(k_merge_finish, dim3(1), dim3(64), 0, dst->stream, dst->scene, res);
-  }
+  if ((st = ordered_insert(dst, m, N, bucketsA, bucketsB, keysA, keysB, plan, exc, excRank, consumes, blockRank, res, tmp, tmpBytes))) return st;
   for (int first = 0; first < N; first += chunk)
     LAUNCH(dst, "merge_pull", k_merge_pull, dim3(gridChunk), dim3(256), m, src->scene, dst->scene, (const unsigned long long *)keysA,
            (const int32_t *)nUnique, first, chunk, (const int32_t *)info, voxels);
@@ -159,6 +172,244 @@ int dsr_merge_volume(dsr_engine *dst, dsr_engine *src, const float src_to_dst_m[
   }
   if (dropped > 0) return fail(DSR_E_OUT_OF_BLOCKS, "merge: dst ran out of voxel blocks / excess list entries; " + std::to_string(dropped) + " blocks dropped");
   return DSR_OK;
+}
+
+}  // extern "C"
+
+// ====================================================================================================================
+// include/dsr_dense.h.  Export: ONE launch of k_dense_export over the grid's tiles.  Import: the candidate box as
+// keys (already in insert order), has-data, the merge's ordered insert, the pull; ONE host wait for the result words.
+
+namespace {
+
+struct DenseCall { DenseP g; long long n; };  // the checked arguments of one call: kernel parameters, grid points
+
+// every DSR_E_ARG of dsr_dense.h; fills c for the export (import_setup below completes it for the import)
+int dense_check(dsr_engine *e, const dsr_dense_grid *grid, const char *what, DenseCall &c) {
+  const std::string w(what);
+  if (!e || !grid) return fail(DSR_E_ARG, w + ": null argument");
+  if (e->s.use_swapping) return fail(DSR_E_ARG, w + ": engines with use_swapping are not supported");
+  if (grid->nx < 1 || grid->ny < 1 || grid->nz < 1) return fail(DSR_E_ARG, w + ": a grid needs at least one point per axis");
+  c.n = (long long)grid->nx * grid->ny;
+  if (c.n > 2147483647ll || (c.n *= grid->nz) > 2147483647ll) return fail(DSR_E_ARG, w + ": more than 2^31 - 1 grid points");
+  if (!std::isfinite(grid->pitch) || grid->pitch <= 0.0f) return fail(DSR_E_ARG, w + ": pitch must be finite and positive");
+  if (std::isnan(grid->mu) || std::isinf(grid->mu)) return fail(DSR_E_ARG, w + ": mu is not finite");
+  if (grid->fill_w < 1 || grid->fill_w > 255) return fail(DSR_E_ARG, w + ": fill_w outside 1..255");
+  if (grid->sampling != DSR_DENSE_NEAREST && grid->sampling != DSR_DENSE_TRILINEAR) return fail(DSR_E_ARG, w + ": unknown sampling");
+  if (grid->import_mode != DSR_DENSE_REPLACE && grid->import_mode != DSR_DENSE_COMBINE) return fail(DSR_E_ARG, w + ": unknown import_mode");
+  if (!rigid_transform(grid->grid_to_world_m)) return fail(DSR_E_ARG, w + ": grid_to_world is not a rigid transform");
+  DenseP &g = c.g;
+  g = DenseP{};
+  const float vs = e->s.voxel_size, muGrid = grid->mu > 0.0f ? grid->mu : e->s.mu;
+  memcpy(g.a.m, grid->grid_to_world_m, sizeof g.a.m);
+  g.scale = grid->pitch / vs;
+  g.tx = g.a.m[12] / vs; g.ty = g.a.m[13] / vs; g.tz = g.a.m[14] / vs;
+  g.ratio = e->s.mu / muGrid;
+  g.nx = grid->nx; g.ny = grid->ny; g.nz = grid->nz;
+  g.trilinear = grid->sampling == DSR_DENSE_TRILINEAR;
+  g.minW = grid->min_w_depth < 1 ? 1 : grid->min_w_depth;
+  g.combine = grid->import_mode == DSR_DENSE_COMBINE;
+  g.fillW = grid->fill_w;
+  g.maxW = e->s.max_w;
+  g.buckets = e->noBuckets; g.mask = (uint32_t)(e->noBuckets - 1);
+  return DSR_OK;
+}
+
+bool misaligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+
+// queue the export (device planes; count may be null)
+void dense_export_queue(dsr_engine *e, const DenseCall &c, float *sdf, uint8_t *wd, uint8_t *rgba, unsigned long long *count) {
+  const long long tiles = (long long)div_up(c.g.nx, kDenseTileX) * div_up(c.g.ny, kDenseTileY) * div_up(c.g.nz, kDenseTileZ);
+  const int grid = (int)std::min<long long>((tiles + 3) / 4, 32768);
+  LAUNCH(e, "dense_export", k_dense_export, dim3(grid), dim3(256), c.g, e->scene, sdf, wd, reinterpret_cast<uint32_t *>(rgba), count);
+}
+
+// the import's part of the parameters: the inverse transform and the candidate box; *N = the candidate blocks
+int dense_import_setup(dsr_engine *e, const dsr_dense_grid *grid, DenseCall &c, int *N) {
+  DenseP &g = c.g;
+  const float vs = e->s.voxel_size, muGrid = grid->mu > 0.0f ? grid->mu : e->s.mu;
+  Mat4 g2w = g.a;
+  if (!dsr_math::m4_inv(g2w.m, g.a.m)) return fail(DSR_E_ARG, "dense import: singular grid_to_world");
+  g.scale = vs / grid->pitch;
+  g.tx = g.a.m[12] / grid->pitch; g.ty = g.a.m[13] / grid->pitch; g.tz = g.a.m[14] / grid->pitch;
+  g.ratio = muGrid / e->s.mu;
+  // dsr_dense.h import step 7: the box [-1, n]^3 of grid indices, corner by corner
+  int lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, hi[3] = {-0x7fffffff, -0x7fffffff, -0x7fffffff};
+  for (int k = 0; k < 8; ++k) {
+    const float cx = (float)((k & 1) ? g.nx : -1) * grid->pitch, cy = (float)((k & 2) ? g.ny : -1) * grid->pitch,
+                cz = (float)((k & 4) ? g.nz : -1) * grid->pitch;
+    const float3 q = mat_mul3(g2w, cx, cy, cz, 1.0f);
+    const int v[3] = {(int)floorf(merge_clamp(q.x / vs)), (int)floorf(merge_clamp(q.y / vs)), (int)floorf(merge_clamp(q.z / vs))};
+    for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], v[a]); hi[a] = std::max(hi[a], v[a]); }
+  }
+  double cap = 1.0;
+  int b0[3], b1[3];
+  for (int a = 0; a < 3; ++a) {
+    b0[a] = std::max((lo[a] - 1) >> 3, -32768);
+    b1[a] = std::min((hi[a] + 1) >> 3, 32767);
+    cap *= (double)std::max(b1[a] - b0[a] + 1, 0);
+  }
+  if (cap >= 2147483647.0) return fail(DSR_E_NOMEM, "dense import: too many candidate blocks for one call");
+  *N = (int)cap;
+  g.hiX = b1[0]; g.hiY = b1[1]; g.hiZ = b1[2];
+  g.cx = std::max(b1[0] - b0[0] + 1, 1); g.cy = std::max(b1[1] - b0[1] + 1, 1);
+  return DSR_OK;
+}
+
+// the import with device planes, after the checks and CHECK_E: everything queued on e's stream, then the one host wait
+int dense_import_run(dsr_engine *e, const DenseCall &c, int N, const float *sdf, const uint8_t *wd, const uint8_t *rgba,
+                     dsr_dense_result *result) {
+  if (result) memset(result, 0, sizeof *result);
+  if (N == 0) return DSR_OK;
+  const DenseP &g = c.g;
+  MergeP m{};  // what the ordered insert reads: the dst fields
+  m.dstBuckets = e->noBuckets; m.dstEntries = e->E; m.dstBlocks = e->noBlocks; m.dstMask = g.mask;
+  Scratch sc("dense import: out of device memory for the candidate lists");
+  unsigned long long *keysA, *keysB, *voxels;
+  uint32_t *bucketsA, *bucketsB;
+  int32_t *info, *exc, *excRank, *consumes, *blockRank, *res;
+  int2 *plan;
+  int st;
+  if ((st = sc.get(&keysA, N)) || (st = sc.get(&keysB, N)) || (st = sc.get(&bucketsA, N)) || (st = sc.get(&bucketsB, N)) ||
+      (st = sc.get(&info, N)) || (st = sc.get(&exc, N)) || (st = sc.get(&excRank, N)) || (st = sc.get(&consumes, N)) ||
+      (st = sc.get(&blockRank, N)) || (st = sc.get(&plan, N)) || (st = sc.get(&res, MR_COUNT)) || (st = sc.get(&voxels, 1)))
+    return st;
+  size_t tmpBytes = 0, b = 0;
+  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, b, bucketsA, bucketsB, keysA, keysB, N, 0, 32, e->stream)); tmpBytes = std::max(tmpBytes, b);
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, b, exc, excRank, N, e->stream)); tmpBytes = std::max(tmpBytes, b);
+  uint8_t *tmp;
+  if ((st = sc.get(&tmp, tmpBytes))) return st;
+
+  HIP_TRY(hipMemsetAsync(voxels, 0, sizeof *voxels, e->stream));
+  LAUNCH(e, "dense_import", k_dense_candidates, dim3(std::min(div_up(N, 256), 4096)), dim3(256), g, keysA, N, res);
+  const int gridW = std::min(div_up(N, 4), 8192);
+  LAUNCH(e, "dense_import", k_dense_has_data, dim3(gridW), dim3(256), g, e->scene, sdf, wd, N, info, bucketsA, res);
+  if ((st = ordered_insert(e, m, N, bucketsA, bucketsB, keysA, keysB, plan, exc, excRank, consumes, blockRank, res, tmp, tmpBytes))) return st;
+  LAUNCH(e, "dense_import", k_dense_pull, dim3(gridW), dim3(256), g, e->scene, sdf, wd, reinterpret_cast<const uint32_t *>(rgba), N,
+         (const int32_t *)info, voxels);
+  HIP_TRY(hipGetLastError());
+
+  // the map has changed: the free-view cache and the cached list of allocated entries are stale
+  e->sceneVersion++;
+  e->allocListVersion = ~0ull;
+  e->fvValid = false;
+
+  int32_t hres[MR_COUNT];
+  unsigned long long hvox = 0;
+  HIP_TRY(hipMemcpyAsync(hres, res, sizeof hres, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(&hvox, voxels, sizeof hvox, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));  // the one host wait
+  const int dropped = hres[MR_NEEDED] - hres[MR_ALLOCATED];
+  if (result) {
+    result->candidate_blocks = N;
+    result->blocks_with_data = hres[MR_WITH_DATA];
+    result->blocks_allocated = hres[MR_ALLOCATED];
+    result->blocks_dropped = dropped;
+    result->voxels_updated = (int64_t)hvox;
+  }
+  if (dropped > 0) return fail(DSR_E_OUT_OF_BLOCKS, "dense import: the engine ran out of voxel blocks / excess list entries; " + std::to_string(dropped) + " blocks dropped");
+  return DSR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t dsr_dense_abi_version(void) { return DSR_DENSE_ABI_VERSION; }
+
+void dsr_dense_default_grid(dsr_dense_grid *g) {
+  if (!g) return;
+  memset(g, 0, sizeof *g);
+  g->nx = g->ny = g->nz = 1;
+  g->grid_to_world_m[0] = g->grid_to_world_m[5] = g->grid_to_world_m[10] = g->grid_to_world_m[15] = 1.0f;
+  g->sampling = DSR_DENSE_TRILINEAR;
+  g->min_w_depth = 1;
+  g->import_mode = DSR_DENSE_REPLACE;
+  g->fill_w = 1;
+}
+
+int dsr_dense_export_dev(dsr_engine *e, const dsr_dense_grid *grid, float *sdf_dev, uint8_t *w_depth_dev, uint8_t *rgba_dev,
+                         dsr_dense_result *result) {
+  DenseCall c;
+  if (int st = dense_check(e, grid, "dense export", c)) return st;
+  if (misaligned(sdf_dev, 4) || misaligned(rgba_dev, 4)) return fail(DSR_E_ARG, "dense export: the sdf and rgba planes must be 4-byte aligned");
+  CHECK_E(e);
+  if (!result) {  // queued; the caller orders its own stream behind the engine's
+    dense_export_queue(e, c, sdf_dev, w_depth_dev, rgba_dev, nullptr);
+    HIP_TRY(hipGetLastError());
+    return DSR_OK;
+  }
+  Scratch sc("dense export: out of device memory");
+  unsigned long long *count, hcount = 0;
+  if (int st = sc.get(&count, 1)) return st;
+  HIP_TRY(hipMemsetAsync(count, 0, sizeof *count, e->stream));
+  dense_export_queue(e, c, sdf_dev, w_depth_dev, rgba_dev, count);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(&hcount, count, sizeof hcount, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  memset(result, 0, sizeof *result);
+  result->points_with_data = (int64_t)hcount;
+  return DSR_OK;
+}
+
+int dsr_dense_export(dsr_engine *e, const dsr_dense_grid *grid, float *sdf, uint8_t *w_depth, uint8_t *rgba, dsr_dense_result *result) {
+  DenseCall c;
+  if (int st = dense_check(e, grid, "dense export", c)) return st;
+  CHECK_E(e);
+  Scratch sc("dense export: out of device memory for the staging buffers");
+  const size_t n = (size_t)c.n;
+  float *dsdf = nullptr;
+  uint8_t *dw = nullptr, *drgba = nullptr;
+  unsigned long long *count, hcount = 0;
+  int st;
+  if ((sdf && (st = sc.get(&dsdf, n))) || (w_depth && (st = sc.get(&dw, n))) || (rgba && (st = sc.get(&drgba, 4 * n))) ||
+      (st = sc.get(&count, 1)))
+    return st;
+  HIP_TRY(hipMemsetAsync(count, 0, sizeof *count, e->stream));
+  dense_export_queue(e, c, dsdf, dw, drgba, count);
+  HIP_TRY(hipGetLastError());
+  if (sdf) HIP_TRY(hipMemcpyAsync(sdf, dsdf, n * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+  if (w_depth) HIP_TRY(hipMemcpyAsync(w_depth, dw, n, hipMemcpyDeviceToHost, e->stream));
+  if (rgba) HIP_TRY(hipMemcpyAsync(rgba, drgba, 4 * n, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(&hcount, count, sizeof hcount, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));  // the one host wait
+  if (result) {
+    memset(result, 0, sizeof *result);
+    result->points_with_data = (int64_t)hcount;
+  }
+  return DSR_OK;
+}
+
+int dsr_dense_import_dev(dsr_engine *e, const dsr_dense_grid *grid, const float *sdf_dev, const uint8_t *w_depth_dev,
+                         const uint8_t *rgba_dev, dsr_dense_result *result) {
+  DenseCall c;
+  int N = 0;
+  if (int st = dense_check(e, grid, "dense import", c)) return st;
+  if (!sdf_dev) return fail(DSR_E_ARG, "dense import: null sdf plane");
+  if (misaligned(sdf_dev, 4) || misaligned(rgba_dev, 4)) return fail(DSR_E_ARG, "dense import: the sdf and rgba planes must be 4-byte aligned");
+  if (int st = dense_import_setup(e, grid, c, &N)) return st;
+  CHECK_E(e);
+  return dense_import_run(e, c, N, sdf_dev, w_depth_dev, rgba_dev, result);
+}
+
+int dsr_dense_import(dsr_engine *e, const dsr_dense_grid *grid, const float *sdf, const uint8_t *w_depth, const uint8_t *rgba,
+                     dsr_dense_result *result) {
+  DenseCall c;
+  int N = 0;
+  if (int st = dense_check(e, grid, "dense import", c)) return st;
+  if (!sdf) return fail(DSR_E_ARG, "dense import: null sdf plane");
+  if (int st = dense_import_setup(e, grid, c, &N)) return st;
+  CHECK_E(e);
+  Scratch sc("dense import: out of device memory for the staging buffers");
+  const size_t n = (size_t)c.n;
+  float *dsdf = nullptr;
+  uint8_t *dw = nullptr, *drgba = nullptr;
+  int st;
+  if ((st = sc.get(&dsdf, n)) || (w_depth && (st = sc.get(&dw, n))) || (rgba && (st = sc.get(&drgba, 4 * n)))) return st;
+  HIP_TRY(hipMemcpyAsync(dsdf, sdf, n * sizeof(float), hipMemcpyHostToDevice, e->stream));
+  if (w_depth) HIP_TRY(hipMemcpyAsync(dw, w_depth, n, hipMemcpyHostToDevice, e->stream));
+  if (rgba) HIP_TRY(hipMemcpyAsync(drgba, rgba, 4 * n, hipMemcpyHostToDevice, e->stream));
+  return dense_import_run(e, c, N, dsdf, dw, drgba, result);
 }
 
 }  // extern "C"

@@ -835,6 +835,116 @@ class EngineCore:
             raise
         return out
 
+    # ---- the volume as a dense grid and back (include/dsr_dense.h; builder-defined)
+    def _dense_api(self):
+        if not hasattr(self, "_dapi"):
+            self._dapi = _capi.bind_dense(self.api.lib, self.api.prefix)
+        if self._dapi is None:
+            raise DsrError(_capi.DSR_E_ARG, f"this backend ({self.api.prefix}*) has no include/dsr_dense.h entry points")
+        return self._dapi
+
+    def _torch_device(self):
+        """the engine's GPU as a torch.device (settings.device -1: the device that was current at creation, taken to be current still)"""
+        import torch
+        return torch.device("cuda", self.settings.device if self.settings.device >= 0 else torch.cuda.current_device())
+
+    def _dense_grid(self, shape, pitch, grid_to_world, mu, sampling, min_w_depth, mode="replace", fill_w=1):
+        """shape: (nz, ny, nx), the shape of the planes as numpy / torch see them"""
+        g = _capi.DenseGrid()
+        self._dense_api().dense_default_grid(C.byref(g))
+        if len(shape) != 3:
+            raise DsrError(_capi.DSR_E_ARG, "a dense grid has three axes (nz, ny, nx)")
+        g.nz, g.ny, g.nx = (int(v) for v in shape)
+        g.pitch = float(pitch)
+        g.mu = 0.0 if mu is None else float(mu)
+        if grid_to_world is not None:
+            g.grid_to_world_m[:] = _colmajor(grid_to_world).tolist()
+        try:
+            g.sampling = {"nearest": _capi.DENSE_NEAREST, "trilinear": _capi.DENSE_TRILINEAR}[sampling]
+            g.import_mode = {"replace": _capi.DENSE_REPLACE, "combine": _capi.DENSE_COMBINE}[mode]
+        except KeyError as err:
+            raise DsrError(_capi.DSR_E_ARG, f"unknown sampling / mode {err}") from None
+        g.min_w_depth, g.fill_w = int(min_w_depth), int(fill_w)
+        return g
+
+    def to_dense(self, shape, pitch, grid_to_world=None, mu=None, sampling="trilinear", min_w_depth=1, colour=True, torch_out=False):
+        """The volume sampled on a lattice of shape = (nz, ny, nx) points, `pitch` metres apart, grid point (ix, iy, iz) at
+        grid_to_world * (ix, iy, iz) * pitch in the engine's world (4x4 row-major, rigid; None: identity) — dsr_dense_export.
+        Returns a dict: "sdf" float32 (nz, ny, nx) in units of `mu` metres (None: the engine's mu; 1.0 where there is no data),
+        "w_depth" uint8 (nz, ny, nx) (0: no data), with colour "rgba" uint8 (nz, ny, nx, 4) = r, g, b, w_color, and
+        "points_with_data".  torch_out: the planes are torch tensors on the engine's GPU, written there directly (complete when
+        the call returns).  Use allocated_bounds() to size a grid.  Reads only."""
+        g = self._dense_grid(shape, pitch, grid_to_world, mu, sampling, min_w_depth)
+        shape = (g.nz, g.ny, g.nx)
+        res = _capi.DenseResult()
+        if torch_out:
+            import torch
+            dev = self._torch_device()
+            out = {"sdf": torch.empty(shape, dtype=torch.float32, device=dev), "w_depth": torch.empty(shape, dtype=torch.uint8, device=dev)}
+            if colour:
+                out["rgba"] = torch.empty(shape + (4,), dtype=torch.uint8, device=dev)
+            self._check(self._dense_api().dense_export_dev(self._h, C.byref(g), out["sdf"].data_ptr(), out["w_depth"].data_ptr(),
+                                                           out["rgba"].data_ptr() if colour else None, C.byref(res)))
+        else:
+            out = {"sdf": np.empty(shape, np.float32), "w_depth": np.empty(shape, np.uint8)}
+            if colour:
+                out["rgba"] = np.empty(shape + (4,), np.uint8)
+            self._check(self._dense_api().dense_export(self._h, C.byref(g), _ptr(out["sdf"]), _ptr(out["w_depth"]),
+                                                       _ptr(out["rgba"]) if colour else None, C.byref(res)))
+        out["points_with_data"] = int(res.points_with_data)
+        return out
+
+    def from_dense(self, sdf, w_depth=None, rgba=None, pitch=None, grid_to_world=None, mu=None, sampling="trilinear", mode="replace",
+                   fill_w=1, min_w_depth=1):
+        """Write a dense grid into the volume, allocating the blocks it lacks (dsr_dense_import): sdf float32 (nz, ny, nx) in units
+        of `mu` metres, w_depth uint8 of the same shape (None: every point has weight fill_w), rgba uint8 (nz, ny, nx, 4) (None: no
+        colour); numpy arrays, or contiguous torch tensors on the engine's GPU.  mode "replace": voxels with data take the sample;
+        "combine": the weighted running mean of the volume merge.  Returns the result as a dict; raises OutOfBlocksError — with the
+        dict as its `result` — when the engine ran out of blocks (what fitted is kept)."""
+        if pitch is None:
+            raise DsrError(_capi.DSR_E_ARG, "from_dense: pitch is required")
+        on_gpu = not isinstance(sdf, np.ndarray) and hasattr(sdf, "data_ptr")
+        g = self._dense_grid(tuple(sdf.shape), pitch, grid_to_world, mu, sampling, min_w_depth, mode, fill_w)
+        shape = (g.nz, g.ny, g.nx)
+        res = _capi.DenseResult()
+        if on_gpu:
+            import torch
+            planes = []
+            for name, t, dtype, want in (("sdf", sdf, torch.float32, shape), ("w_depth", w_depth, torch.uint8, shape), ("rgba", rgba, torch.uint8, shape + (4,))):
+                if t is None:
+                    planes.append(None)
+                    continue
+                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == self._torch_device() and t.dtype == dtype and
+                        tuple(t.shape) == want and t.is_contiguous()):
+                    raise DsrError(_capi.DSR_E_ARG, f"from_dense: {name} must be a contiguous {dtype} tensor of shape {want} on the engine's GPU")
+                planes.append(t)
+            self.wait_for_stream(torch.cuda.current_stream(self._torch_device()).cuda_stream)  # the tensors' producers first
+            status = self._dense_api().dense_import_dev(self._h, C.byref(g), *(t.data_ptr() if t is not None else None for t in planes),
+                                                        C.byref(res))
+        else:
+            planes = [np.ascontiguousarray(sdf, np.float32), None if w_depth is None else np.ascontiguousarray(w_depth, np.uint8),
+                      None if rgba is None else np.ascontiguousarray(rgba, np.uint8)]
+            for a, want in zip(planes, (shape, shape, shape + (4,))):
+                if a is not None and a.shape != want:
+                    raise DsrError(_capi.DSR_E_ARG, f"from_dense: a plane of shape {a.shape}, expected {want}")
+            status = self._dense_api().dense_import(self._h, C.byref(g), *(_ptr(a) if a is not None else None for a in planes), C.byref(res))
+        out = {k: int(getattr(res, k)) for k in ("candidate_blocks", "blocks_with_data", "blocks_allocated", "blocks_dropped", "voxels_updated")}
+        try:
+            self._check(status)
+        except OutOfBlocksError as err:
+            err.result = out
+            raise
+        return out
+
+    def allocated_bounds(self):
+        """(min, max) block position (x, y, z; int arrays) over the allocated entries of the table, or None for an empty volume: the
+        voxels 8 * min .. 8 * max + 7 hold the map — what sizes a grid for to_dense."""
+        t = self.dump_hash_table()
+        pos = t["pos"][t["ptr"] >= 0].astype(np.int64)
+        if not len(pos):
+            return None
+        return pos.min(0), pos.max(0)
+
     # ---- aligning another volume to this one (include/dsr_align.h, DESIGN.md §18; builder-defined)
     def _align_api(self):
         if not hasattr(self, "_aapi"):
@@ -1106,6 +1216,16 @@ class InfiniTamDriver:
         the rigid transform src_to_dst (other's world -> this world) — what a host calls before it frees a pruned track's
         reconstruction.  Returns the merge result as a dict."""
         return self.core.merge_from(other.core, src_to_dst)
+
+    def ExportDense(self, shape, pitch, grid_to_world=None, **kwargs):
+        """ITMMainEngine::ExportDense (builder-defined, include/dsr_dense.h): the volume sampled on a regular lattice —
+        EngineCore.to_dense's dict of planes (INTEGRATION.md "dense grids")."""
+        return self.core.to_dense(shape, pitch, grid_to_world, **kwargs)
+
+    def ImportDense(self, sdf, w_depth=None, rgba=None, **kwargs):
+        """ITMMainEngine::ImportDense (builder-defined, include/dsr_dense.h): a dense grid written into the volume —
+        EngineCore.from_dense's result dict; raises OutOfBlocksError on exhaustion like Integrate (what fitted is kept)."""
+        return self.core.from_dense(sdf, w_depth, rgba, **kwargs)
 
     def AlignFrom(self, other, init_src_to_dst, **params):
         """ITMMainEngine::AlignFrom (builder-defined, include/dsr_align.h): the transform other's world -> this world, refined from

@@ -29,6 +29,7 @@
 #include "../include/dsr_mesh.h"
 #include "../include/dsr_merge.h"
 #include "../include/dsr_align.h"
+#include "../include/dsr_dense.h"
 
 // The tracker's entry points are referenced WEAKLY: a host linked against a library without them (the CPU oracle's orc_* build
 // of the reference's hosts) still links, and ITMTrackingController::Track then throws as it did before the tracker existed.
@@ -53,6 +54,11 @@ int dsr_save_scene_to_mesh_indexed(dsr_engine *e, const char *path, int flags) _
 // ... and the volume merge's (include/dsr_merge.h): MergeFrom throws on a library without it
 int dsr_merge_volume(dsr_engine *dst, dsr_engine *src, const float src_to_dst_m[16], const dsr_merge_params *params,
                      dsr_merge_result *result) __attribute__((weak));
+// ... and the dense grids' (include/dsr_dense.h): ExportDense / ImportDense throw on a library without them
+int dsr_dense_export(dsr_engine *e, const dsr_dense_grid *grid, float *sdf, uint8_t *w_depth, uint8_t *rgba, dsr_dense_result *result) __attribute__((weak));
+int dsr_dense_import(dsr_engine *e, const dsr_dense_grid *grid, const float *sdf, const uint8_t *w_depth, const uint8_t *rgba,
+                     dsr_dense_result *result) __attribute__((weak));
+void dsr_dense_default_grid(dsr_dense_grid *g) __attribute__((weak));
 // ... and the volume alignment's (include/dsr_align.h): AlignFrom throws on a library without it
 int dsr_align_volume(dsr_engine *dst, dsr_engine *src, const float init_src_to_dst_m[16], const dsr_align_params *params,
                      dsr_align_result *result, dsr_align_log_entry *log, int32_t log_capacity, int32_t *log_count) __attribute__((weak));
@@ -655,6 +661,29 @@ class ITMMainEngine {
     dsr_merge_result res;
     memset(&res, 0, sizeof res);
     ITMLib::Engine::dsr_throw(dsr_merge_volume(engine_, other.engine_, src_to_dst.m, nullptr, &res));
+    return res;
+  }
+  // BUILDER-DEFINED (include/dsr_dense.h): the volume sampled on the lattice `grid` describes into host planes of
+  // grid.nx * grid.ny * grid.nz points (any of them may be null), and such planes written into the volume, allocating what it
+  // lacks.  DefaultDenseGrid gives the defaults to start from.  ImportDense throws on exhaustion like Integrate (what fitted is kept).
+  static dsr_dense_grid DefaultDenseGrid() {
+    if (!dsr_dense_default_grid) throw std::runtime_error("this library has no dense grids (include/dsr_dense.h)");
+    dsr_dense_grid g;
+    dsr_dense_default_grid(&g);
+    return g;
+  }
+  dsr_dense_result ExportDense(const dsr_dense_grid &grid, float *sdf, uint8_t *w_depth, uint8_t *rgba) {
+    if (!dsr_dense_export) throw std::runtime_error("this library has no dense grids (include/dsr_dense.h)");
+    dsr_dense_result res;
+    memset(&res, 0, sizeof res);
+    ITMLib::Engine::dsr_throw(dsr_dense_export(engine_, &grid, sdf, w_depth, rgba, &res));
+    return res;
+  }
+  dsr_dense_result ImportDense(const dsr_dense_grid &grid, const float *sdf, const uint8_t *w_depth, const uint8_t *rgba) {
+    if (!dsr_dense_import) throw std::runtime_error("this library has no dense grids (include/dsr_dense.h)");
+    dsr_dense_result res;
+    memset(&res, 0, sizeof res);
+    ITMLib::Engine::dsr_throw(dsr_dense_import(engine_, &grid, sdf, w_depth, rgba, &res));
     return res;
   }
   // BUILDER-DEFINED (include/dsr_align.h): the transform other's world -> this one's, refined from `init` by
