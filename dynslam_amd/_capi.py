@@ -600,3 +600,48 @@ def bind_dense(lib, prefix):
     if ns.dense_abi_version() != DENSE_ABI_VERSION:
         raise ImportError("dense ABI version mismatch (include/dsr_dense.h)")
     return ns
+
+
+# ---- include/dsr_esdf.h: an exact Euclidean signed distance field from a dense grid.  A table of its own, like the dense grids'.
+ESDF_ABI_VERSION = 1  # == DSR_ESDF_ABI_VERSION
+ESDF_FAR = 2147483647  # DSR_ESDF_FAR
+ESDF_HAS_DATA, ESDF_SITE_OUT, ESDF_SITE_IN, ESDF_FAR_FLAG, ESDF_FROM_TSDF = 1, 2, 4, 8, 16  # DSR_ESDF_* flag bits
+
+
+class EsdfParams(C.Structure):  # struct dsr_esdf_params
+    _fields_ = [("max_steps", C.c_int32), ("min_w_depth", C.c_int32), ("keep_tsdf", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+class EsdfResult(C.Structure):  # struct dsr_esdf_result
+    _fields_ = [("points_with_data", C.c_int64), ("outside_sites", C.c_int64), ("inside_sites", C.c_int64), ("band_points", C.c_int64),
+                ("far_points", C.c_int64), ("reserved", C.c_int32 * 4)]
+
+
+assert C.sizeof(EsdfParams) == 32 and C.sizeof(EsdfResult) == 56
+
+_ESDF_PLANES = [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(EsdfParams),
+                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EsdfResult)]
+_ESDF_EXPORT = [_H, C.POINTER(DenseGrid), C.POINTER(EsdfParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EsdfResult)]
+ESDF_SIGNATURES = {
+    "esdf_abi_version": (C.c_int32, []),
+    "esdf_default_params": (None, [C.POINTER(EsdfParams)]),
+    "esdf_from_planes_dev": (C.c_int, _ESDF_PLANES),
+    "esdf_from_planes": (C.c_int, _ESDF_PLANES),
+    "esdf_export": (C.c_int, _ESDF_EXPORT),
+    "esdf_export_dev": (C.c_int, _ESDF_EXPORT),
+}
+
+
+def bind_esdf(lib, prefix):
+    """The ESDF entry points `prefix + name` in `lib`, or None when the library has none (the CPU oracle)."""
+    if not hasattr(lib, prefix + "esdf_export"):
+        return None
+    ns = SimpleNamespace()
+    for name, (res, args) in ESDF_SIGNATURES.items():
+        fn = getattr(lib, prefix + name)
+        fn.restype = res
+        fn.argtypes = args
+        setattr(ns, name, fn)
+    if ns.esdf_abi_version() != ESDF_ABI_VERSION:
+        raise ImportError("esdf ABI version mismatch (include/dsr_esdf.h)")
+    return ns

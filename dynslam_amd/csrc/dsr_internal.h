@@ -13,6 +13,7 @@
 //   dsr_align.hip     aligning one volume to another, SDF to SDF (include/dsr_align.h): the list of blocks, the queued evaluations
 //   dsr_mesh_indexed.hip  the indexed mesh's entry points (include/dsr_mesh.h): flags, getters, the PLY / OBJ writers.  Host code only:
 //                     its kernels (k_mesh_indexed.h) build on the mesher's policies and scans, so dsr_engine.hip holds their launches
+//   dsr_esdf.hip      an exact Euclidean signed distance field from a dense grid (include/dsr_esdf.h): the checks, three launches
 // Every kernel header (k_*.h) is included by exactly ONE of them: kernels have external linkage.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -376,12 +377,18 @@ int device_alloc(T **p, size_t n) {
 struct Scratch {  // everything such a call allocates; freed when it leaves
   const char *what;  // the message of DSR_E_NOMEM
   std::vector<void *> ptrs;
+  // ordered: taken and released in the order of `stream` (hipMallocAsync / hipFreeAsync) — for a call that queues its work and
+  // must return without waiting for it, which hipFree would (dsr_esdf.hip)
+  hipStream_t stream = nullptr;
+  bool ordered = false;
   explicit Scratch(const char *what_) : what(what_) {}
-  ~Scratch() { for (void *p : ptrs) (void)hipFree(p); }
+  Scratch(const char *what_, hipStream_t stream_) : what(what_), stream(stream_), ordered(true) {}
+  ~Scratch() { for (void *p : ptrs) (void)(ordered ? hipFreeAsync(p, stream) : hipFree(p)); }
   template <class T>
   int get(T **p, size_t n) {
     void *q = nullptr;
-    if (hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); return fail(DSR_E_NOMEM, what); }
+    const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
+    if ((ordered ? hipMallocAsync(&q, bytes, stream) : hipMalloc(&q, bytes)) != hipSuccess) { (void)hipGetLastError(); return fail(DSR_E_NOMEM, what); }
     ptrs.push_back(q);
     *p = static_cast<T *>(q);
     return DSR_OK;

@@ -115,6 +115,34 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+# the output planes of include/dsr_esdf.h in the order of its entry points, with their element types (numpy and torch share the names)
+ESDF_PLANES = {"dist": "float32", "flags": "uint8", "d2_out": "int32", "d2_in": "int32"}
+ESDF_RESULT_KEYS = ("points_with_data", "outside_sites", "inside_sites", "band_points", "far_points")
+
+
+def _esdf_plane_names(planes):
+    names = tuple(planes)
+    for k in names:
+        if k not in ESDF_PLANES:
+            raise DsrError(_capi.DSR_E_ARG, f"unknown esdf plane {k!r}: one of {tuple(ESDF_PLANES)}")
+    return names
+
+
+def esdf_params(api, pitch, max_distance=None, max_steps=32, min_w_depth=1, keep_tsdf=True):
+    """dsr_esdf_params: max_distance (metres) becomes max_steps = ceil(max_distance / pitch), clamped to 1..2048"""
+    p = _capi.EsdfParams()
+    api.esdf_default_params(C.byref(p))
+    if max_distance is not None:
+        ratio = float(max_distance) / float(pitch) if float(pitch) > 0 else 1.0
+        max_steps = min(max(int(np.ceil(ratio)) if np.isfinite(ratio) else 2048, 1), 2048)
+    p.max_steps, p.min_w_depth, p.keep_tsdf = int(max_steps), int(min_w_depth), int(bool(keep_tsdf))
+    return p
+
+
+def esdf_result_dict(res):
+    return {k: int(getattr(res, k)) for k in ESDF_RESULT_KEYS}
+
+
 class Exchange:
     """The fused-preview exchange of include/dsr.h (`dsr_exchange_*`): layer buffers on every GPU this process drives, the RCCL
     all-gather between them (called by the library itself) and the composite.  `devices`: one process drives all GPUs, rank r
@@ -945,6 +973,43 @@ class EngineCore:
             return None
         return pos.min(0), pos.max(0)
 
+    # ---- the volume's Euclidean signed distance field on a dense grid (include/dsr_esdf.h; builder-defined)
+    def _esdf_api(self):
+        if not hasattr(self, "_eapi"):
+            self._eapi = _capi.bind_esdf(self.api.lib, self.api.prefix)
+        if self._eapi is None:
+            raise DsrError(_capi.DSR_E_ARG, f"this backend ({self.api.prefix}*) has no include/dsr_esdf.h entry points")
+        return self._eapi
+
+    def to_esdf(self, shape, pitch, grid_to_world=None, *, max_distance=None, max_steps=32, mu=None, sampling="trilinear", min_w_depth=1,
+                keep_tsdf=True, planes=("dist", "flags"), torch_out=False):
+        """The volume's exact Euclidean signed distance field on the lattice of to_dense (shape = (nz, ny, nx), `pitch` metres,
+        grid_to_world) — dsr_esdf_export: the dense export into scratch planes, then the distance transform to the grid points at
+        which the sdf changes sign, out to max_steps grid steps (or max_distance metres: ceil(max_distance / pitch), clamped to
+        1..2048).  Returns a dict of the `planes` asked for — "dist" float32 metres (negative behind the surface; +-max_steps * pitch
+        where no surface is within reach), "flags" uint8 (_capi.ESDF_* bits), "d2_out" / "d2_in" int32 squared grid steps to the
+        nearest site in front of / behind the surface (_capi.ESDF_FAR: none within reach) — plus the counts of dsr_esdf_result.
+        keep_tsdf: inside the band the TSDF's own value is the distance.  torch_out: torch tensors on the engine's GPU, complete
+        when the call returns.  Reads only."""
+        api = self._esdf_api()
+        g = self._dense_grid(shape, pitch, grid_to_world, mu, sampling, min_w_depth)
+        p = esdf_params(api, pitch, max_distance, max_steps, min_w_depth, keep_tsdf)
+        shape = (g.nz, g.ny, g.nx)
+        res = _capi.EsdfResult()
+        names = _esdf_plane_names(planes)
+        if torch_out:
+            import torch
+            dev = self._torch_device()
+            out = {k: torch.empty(shape, dtype=getattr(torch, ESDF_PLANES[k]), device=dev) for k in names}
+            ptrs = [out[k].data_ptr() if k in out else None for k in ESDF_PLANES]
+            self._check(api.esdf_export_dev(self._h, C.byref(g), C.byref(p), *ptrs, C.byref(res)))
+        else:
+            out = {k: np.empty(shape, ESDF_PLANES[k]) for k in names}
+            ptrs = [_ptr(out[k]) if k in out else None for k in ESDF_PLANES]
+            self._check(api.esdf_export(self._h, C.byref(g), C.byref(p), *ptrs, C.byref(res)))
+        out.update(esdf_result_dict(res))
+        return out
+
     # ---- aligning another volume to this one (include/dsr_align.h, DESIGN.md §18; builder-defined)
     def _align_api(self):
         if not hasattr(self, "_aapi"):
@@ -1221,6 +1286,11 @@ class InfiniTamDriver:
         """ITMMainEngine::ExportDense (builder-defined, include/dsr_dense.h): the volume sampled on a regular lattice —
         EngineCore.to_dense's dict of planes (INTEGRATION.md "dense grids")."""
         return self.core.to_dense(shape, pitch, grid_to_world, **kwargs)
+
+    def ExportEsdf(self, shape, pitch, grid_to_world=None, **kwargs):
+        """ITMMainEngine::ExportEsdf (builder-defined, include/dsr_esdf.h): the volume's Euclidean signed distance field on a
+        regular lattice — EngineCore.to_esdf's dict of planes and counts (INTEGRATION.md "distance fields")."""
+        return self.core.to_esdf(shape, pitch, grid_to_world, **kwargs)
 
     def ImportDense(self, sdf, w_depth=None, rgba=None, **kwargs):
         """ITMMainEngine::ImportDense (builder-defined, include/dsr_dense.h): a dense grid written into the volume —

@@ -30,6 +30,7 @@
 #include "../include/dsr_merge.h"
 #include "../include/dsr_align.h"
 #include "../include/dsr_dense.h"
+#include "../include/dsr_esdf.h"
 
 // The tracker's entry points are referenced WEAKLY: a host linked against a library without them (the CPU oracle's orc_* build
 // of the reference's hosts) still links, and ITMTrackingController::Track then throws as it did before the tracker existed.
@@ -59,6 +60,10 @@ int dsr_dense_export(dsr_engine *e, const dsr_dense_grid *grid, float *sdf, uint
 int dsr_dense_import(dsr_engine *e, const dsr_dense_grid *grid, const float *sdf, const uint8_t *w_depth, const uint8_t *rgba,
                      dsr_dense_result *result) __attribute__((weak));
 void dsr_dense_default_grid(dsr_dense_grid *g) __attribute__((weak));
+// ... and the distance fields' (include/dsr_esdf.h): ExportEsdf throws on a library without them
+int dsr_esdf_export(dsr_engine *e, const dsr_dense_grid *grid, const dsr_esdf_params *params, float *dist, uint8_t *flags,
+                    int32_t *d2_out, int32_t *d2_in, dsr_esdf_result *result) __attribute__((weak));
+void dsr_esdf_default_params(dsr_esdf_params *p) __attribute__((weak));
 // ... and the volume alignment's (include/dsr_align.h): AlignFrom throws on a library without it
 int dsr_align_volume(dsr_engine *dst, dsr_engine *src, const float init_src_to_dst_m[16], const dsr_align_params *params,
                      dsr_align_result *result, dsr_align_log_entry *log, int32_t log_capacity, int32_t *log_count) __attribute__((weak));
@@ -677,6 +682,23 @@ class ITMMainEngine {
     dsr_dense_result res;
     memset(&res, 0, sizeof res);
     ITMLib::Engine::dsr_throw(dsr_dense_export(engine_, &grid, sdf, w_depth, rgba, &res));
+    return res;
+  }
+  // BUILDER-DEFINED (include/dsr_esdf.h): the volume's exact Euclidean signed distance field on the lattice `grid`
+  // describes, into host planes of grid.nx * grid.ny * grid.nz points (any of them may be null).  DefaultEsdfParams gives the
+  // defaults to start from.  Reads only.
+  static dsr_esdf_params DefaultEsdfParams() {
+    if (!dsr_esdf_default_params) throw std::runtime_error("this library has no distance fields (include/dsr_esdf.h)");
+    dsr_esdf_params p;
+    dsr_esdf_default_params(&p);
+    return p;
+  }
+  dsr_esdf_result ExportEsdf(const dsr_dense_grid &grid, const dsr_esdf_params &params, float *dist, uint8_t *flags, int32_t *d2_out,
+                             int32_t *d2_in) {
+    if (!dsr_esdf_export) throw std::runtime_error("this library has no distance fields (include/dsr_esdf.h)");
+    dsr_esdf_result res;
+    memset(&res, 0, sizeof res);
+    ITMLib::Engine::dsr_throw(dsr_esdf_export(engine_, &grid, &params, dist, flags, d2_out, d2_in, &res));
     return res;
   }
   dsr_dense_result ImportDense(const dsr_dense_grid &grid, const float *sdf, const uint8_t *w_depth, const uint8_t *rgba) {
