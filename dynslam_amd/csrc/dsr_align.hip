@@ -35,11 +35,7 @@ void dsr_align_default_params(dsr_align_params *p) {
 
 int dsr_align_volume(dsr_engine *dst, dsr_engine *src, const float init_src_to_dst_m[16], const dsr_align_params *params,
                      dsr_align_result *result, dsr_align_log_entry *log, int32_t log_capacity, int32_t *log_count) {
-  if (!dst || !src || !init_src_to_dst_m) return fail(DSR_E_ARG, "align: null argument");
-  if (dst == src) return fail(DSR_E_ARG, "align: dst and src are the same engine");
-  if (dst->device != src->device) return fail(DSR_E_ARG, "align: the engines sit on different devices (move one with dsr_snapshot_export / _import)");
-  if (dst->s.use_swapping || src->s.use_swapping) return fail(DSR_E_ARG, "align: engines with use_swapping are not supported");
-  if (!rigid_transform(init_src_to_dst_m)) return fail(DSR_E_ARG, "align: init_src_to_dst is not a rigid transform");
+  if (int st = two_volume_check(dst, src, init_src_to_dst_m, "align", "init_src_to_dst")) return st;
   if (log_capacity < 0 || (log && log_capacity == 0)) return fail(DSR_E_ARG, "align: a log needs a log_capacity > 0");
   dsr_align_params prm;
   dsr_align_default_params(&prm);
@@ -86,12 +82,7 @@ int dsr_align_volume(dsr_engine *dst, dsr_engine *src, const float init_src_to_d
   HIP_TRY(hipcub::DeviceSelect::If(nullptr, tmpBytes, entries, list, nList, src->E, isAllocated, dst->stream));
   if ((st = sc.get(&tmp, tmpBytes))) return st;
 
-  // src's queued work before the first read of it (as dsr_stream_wait_for_engine orders a foreign stream)
-  if (src->stream != dst->stream) {
-    if (!src->orderEvent) HIP_TRY(hipEventCreateWithFlags(&src->orderEvent, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(src->orderEvent, src->stream));
-    HIP_TRY(hipStreamWaitEvent(dst->stream, src->orderEvent, 0));
-  }
+  if ((st = order_after(dst, src))) return st;
   {
     ProfScope ps(dst, "align_list");
     HIP_TRY(hipcub::DeviceSelect::If(tmp, tmpBytes, entries, list, nList, src->E, isAllocated, dst->stream));

@@ -170,6 +170,35 @@ __host__ __device__ __forceinline__ float sdf_to_float(float v) { return v / 327
 __host__ __device__ __forceinline__ float sdf_to_float_short(float v) { return div_short(v, 32767.0f, 1.0f / 32767.0f); }
 __device__ __forceinline__ short sdf_from_float(float f) { return (short)f2i(f * 32767.0f); }
 
+// ITMSwappingEngine.h combineVoxelDepthInformation on one voxel: (sdf, w) of the local block <- its merge with the stored copy's
+// (oldSdf, oldW).  Shared by the swap-in (k_swap.h), the complete mesher (k_mesh_complete.h), which needs the sdf the next swap-in
+// WOULD leave, and the pull of a merge or a dense import (k_merge.h), where the incoming sample plays the stored copy.
+__device__ __forceinline__ void combine_voxel_depth(short oldSdf, int oldW, int maxW, short &sdf, int &w) {
+  if (oldW == 0) return;
+  float newF = sdf_to_float((float)sdf);
+  const float oldF = sdf_to_float((float)oldSdf);
+  newF = (float)oldW * oldF + (float)w * newF;
+  w = oldW + w;
+  newF /= (float)w;
+  w = w < maxW ? w : maxW;
+  sdf = sdf_from_float(newF);
+}
+// ... combineVoxelColorInformation, on the (r, g, b, w_color) word
+__device__ __forceinline__ uchar4 combine_voxel_colour(uchar4 sc, uchar4 dc, int maxW) {
+  int newW = dc.w;
+  const int oldW = sc.w;
+  if (oldW == 0) return dc;
+  float nx = (float)dc.x / 255.0f, ny = (float)dc.y / 255.0f, nz = (float)dc.z / 255.0f;
+  const float ox = (float)sc.x / 255.0f, oy = (float)sc.y / 255.0f, oz = (float)sc.z / 255.0f;
+  nx = ox * (float)oldW + nx * (float)newW;
+  ny = oy * (float)oldW + ny * (float)newW;
+  nz = oz * (float)oldW + nz * (float)newW;
+  newW = oldW + newW;
+  nx /= (float)newW; ny /= (float)newW; nz /= (float)newW;
+  newW = newW < maxW ? newW : maxW;
+  return make_uchar4((uint8_t)f2i(nx * 255.0f), (uint8_t)f2i(ny * 255.0f), (uint8_t)f2i(nz * 255.0f), (uint8_t)newW);
+}
+
 // The per-pixel / per-block functions of the range-image, visibility, raycast and shading kernels are templates over an Ops
 // policy — how to convert float -> int, round down / up, divide by a tame divisor, ask "any ray of the wave" —: the device's
 // instructions here, a one-ray host stand-in in tests/hostsim, under which tests/test_device_functions_host.py runs those very functions

@@ -220,10 +220,10 @@ int dsr_composite_instances(uint8_t *target_rgba, float *target_depth, const uin
   float *tD = nullptr, *lD = nullptr;
   int st = DSR_OK;
   auto cleanup = [&]() { if (tR) (void)hipFree(tR); if (lR) (void)hipFree(lR); if (tD) (void)hipFree(tD); if (lD) (void)hipFree(lD); };
-  if ((st = dsr_internal::device_alloc(&tD, P))) { cleanup(); return st; }
-  if (L && (st = dsr_internal::device_alloc(&lD, P * L))) { cleanup(); return st; }
-  if (target_rgba && (st = dsr_internal::device_alloc(&tR, P))) { cleanup(); return st; }
-  if (target_rgba && L && (st = dsr_internal::device_alloc(&lR, P * L))) { cleanup(); return st; }
+  if ((st = dsr_internal::dmalloc(&tD, P))) { cleanup(); return st; }
+  if (L && (st = dsr_internal::dmalloc(&lD, P * L))) { cleanup(); return st; }
+  if (target_rgba && (st = dsr_internal::dmalloc(&tR, P))) { cleanup(); return st; }
+  if (target_rgba && L && (st = dsr_internal::dmalloc(&lR, P * L))) { cleanup(); return st; }
 #define CP(expr) if ((expr) != hipSuccess) { cleanup(); return fail(DSR_E_DEVICE, "composite copy failed"); }
   CP(hipMemcpy(tD, target_depth, P * 4, hipMemcpyHostToDevice));
   if (L) CP(hipMemcpy(lD, layers_depth, P * L * 4, hipMemcpyHostToDevice));

@@ -14,7 +14,8 @@
 //   dsr_mesh_indexed.hip  the indexed mesh's entry points (include/dsr_mesh.h): flags, getters, the PLY / OBJ writers.  Host code only:
 //                     its kernels (k_mesh_indexed.h) build on the mesher's policies and scans, so dsr_engine.hip holds their launches
 //   dsr_esdf.hip      an exact Euclidean signed distance field from a dense grid (include/dsr_esdf.h): the checks, three launches
-// Every kernel header (k_*.h) is included by exactly ONE of them: kernels have external linkage.
+// Every KERNEL header (k_*.h) is included by exactly ONE of them: __global__ kernels have external linkage.  Headers that hold only
+// inline device functions (dsr_device.h, dsr_math.h, dsr_sample.h) are shared: any unit may include them.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -368,11 +369,6 @@ int engine_mesh_indexed_release(dsr_engine *e);
 bool host_range_pinned(const void *p, size_t bytes);
 // dsr_profile.hip: div_short(x, b) == x / b for every x? (k_integrate.h; checked once per engine for its mu)
 int short_division_exact(hipStream_t stream, float b, bool *exact);
-template <class T>
-int device_alloc(T **p, size_t n) {
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(p), n * sizeof(T)));
-  return DSR_OK;
-}
 // ---- shared by the calls that read one volume against another (dsr_merge.hip, dsr_align.hip)
 struct Scratch {  // everything such a call allocates; freed when it leaves
   const char *what;  // the message of DSR_E_NOMEM
@@ -394,6 +390,14 @@ struct Scratch {  // everything such a call allocates; freed when it leaves
     return DSR_OK;
   }
 };
+// src's queued work before dst's stream first reads src (as dsr_stream_wait_for_engine orders a foreign stream)
+inline int order_after(dsr_engine *dst, dsr_engine *src) {
+  if (src->stream == dst->stream) return DSR_OK;
+  if (!src->orderEvent) HIP_TRY(hipEventCreateWithFlags(&src->orderEvent, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(src->orderEvent, src->stream));
+  HIP_TRY(hipStreamWaitEvent(dst->stream, src->orderEvent, 0));
+  return DSR_OK;
+}
 // finite, affine, and rigid within what the allocation's step bound allows (dsr_engine_create: rays 5 % longer than a rigid pose
 // makes them): no element of R^T R - I beyond 0.1
 inline bool rigid_transform(const float *m) {
@@ -406,6 +410,16 @@ inline bool rigid_transform(const float *m) {
       if (std::fabs(d - (a == b ? 1.0 : 0.0)) > 0.1) return false;
     }
   return true;
+}
+// what such a call asks of its two engines and of the transform m (named mName in the message) between them; w: "merge" / "align"
+inline int two_volume_check(const dsr_engine *dst, const dsr_engine *src, const float *m, const char *what, const char *mName) {
+  const std::string w(what);
+  if (!dst || !src || !m) return fail(DSR_E_ARG, w + ": null argument");
+  if (dst == src) return fail(DSR_E_ARG, w + ": dst and src are the same engine");
+  if (dst->device != src->device) return fail(DSR_E_ARG, w + ": the engines sit on different devices (move one with dsr_snapshot_export / _import)");
+  if (dst->s.use_swapping || src->s.use_swapping) return fail(DSR_E_ARG, w + ": engines with use_swapping are not supported");
+  if (!rigid_transform(m)) return fail(DSR_E_ARG, w + ": " + mName + " is not a rigid transform");
+  return DSR_OK;
 }
 }  // namespace dsr_internal
 using dsr_internal::host_range_pinned;

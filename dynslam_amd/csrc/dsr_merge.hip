@@ -31,25 +31,71 @@ int boxes_per_axis(const float *m, int row, double vsSrc, double vsDst) {
   return (int)std::floor(ext / 8.0) + 2;
 }
 
+// What a call that pulls data into a volume allocates for its N candidate blocks (freed when it leaves): per candidate the key and
+// the bucket (A: as the passes write them, B: sorted by the insert), info (k_merge.h has_data_body), the insert's plan .. blockRank;
+// the result words (MR_*) with the number of unique keys behind them, the voxel counter; hipCUB's temporary storage, large
+// enough for every hipCUB call of ordered_insert and — withSort — for the merge's sort + unique of the keys.
+struct InsertScratch {
+  Scratch sc;
+  unsigned long long *keysA, *keysB, *voxels;
+  uint32_t *bucketsA, *bucketsB;
+  int32_t *info, *exc, *excRank, *consumes, *blockRank, *res, *nUnique;
+  int2 *plan;
+  uint8_t *tmp;
+  size_t tmpBytes = 0;
+  explicit InsertScratch(const char *what) : sc(what) {}
+  int init(int N, bool withSort, hipStream_t stream) {
+    int st;
+    if ((st = sc.get(&keysA, N)) || (st = sc.get(&keysB, N)) || (st = sc.get(&bucketsA, N)) || (st = sc.get(&bucketsB, N)) ||
+        (st = sc.get(&info, N)) || (st = sc.get(&exc, N)) || (st = sc.get(&excRank, N)) || (st = sc.get(&consumes, N)) ||
+        (st = sc.get(&blockRank, N)) || (st = sc.get(&plan, N)) || (st = sc.get(&res, MR_COUNT + 1)) || (st = sc.get(&voxels, 1)))
+      return st;
+    nUnique = res + MR_COUNT;
+    size_t b = 0;
+    if (withSort) {
+      HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, b, keysA, keysB, N, 0, 49, stream)); tmpBytes = std::max(tmpBytes, b);
+      HIP_TRY(hipcub::DeviceSelect::Unique(nullptr, b, keysB, keysA, nUnique, N, stream)); tmpBytes = std::max(tmpBytes, b);
+    }
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, b, bucketsA, bucketsB, keysA, keysB, N, 0, 32, stream)); tmpBytes = std::max(tmpBytes, b);
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, b, exc, excRank, N, stream)); tmpBytes = std::max(tmpBytes, b);
+    if ((st = sc.get(&tmp, tmpBytes))) return st;
+    HIP_TRY(hipMemsetAsync(voxels, 0, sizeof *voxels, stream));
+    return DSR_OK;
+  }
+};
+
 // The ordered insert of the candidates dst lacks (dsr_merge.h step 3), queued on dst's stream: a stable sort by bucket (the key
 // order survives inside a bucket), plan, two exclusive sums, apply, finish.  bucketsA / keysA: per candidate its bucket
-// (kMergeNoBucket: nothing to insert) and key; the B arrays, plan .. blockRank: N elements of scratch; m: the dst fields.
-int ordered_insert(dsr_engine *dst, const MergeP &m, int N, uint32_t *bucketsA, uint32_t *bucketsB, unsigned long long *keysA,
-                   unsigned long long *keysB, int2 *plan, int32_t *exc, int32_t *excRank, int32_t *consumes, int32_t *blockRank,
-                   int32_t *res, uint8_t *tmp, size_t tmpBytes) {
+// (kMergeNoBucket: nothing to insert) and key; m: the dst fields.
+int ordered_insert(dsr_engine *dst, const MergeP &m, int N, const InsertScratch &s) {
   ProfScope ps(dst, "merge_alloc");
-  size_t b = tmpBytes;
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, b, bucketsA, bucketsB, keysA, keysB, N, 0, 32, dst->stream));
+  size_t b = s.tmpBytes;
+  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(s.tmp, b, s.bucketsA, s.bucketsB, s.keysA, s.keysB, N, 0, 32, dst->stream));
   const dim3 g(div_up(N, 256));
-  hipLaunchKernelGGL(k_merge_plan, g, dim3(256), 0, dst->stream, m, dst->scene, (const uint32_t *)bucketsB, N, plan, exc, res);
-  b = tmpBytes; HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, b, exc, excRank, N, dst->stream));
-  hipLaunchKernelGGL(k_merge_consume, g, dim3(256), 0, dst->stream, (const uint32_t *)bucketsB, N, (const int32_t *)exc,
-                     (const int32_t *)excRank, (const int32_t *)res, consumes);
-  b = tmpBytes; HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, b, consumes, blockRank, N, dst->stream));
-  hipLaunchKernelGGL(k_merge_apply, g, dim3(256), 0, dst->stream, m, dst->scene, (const uint32_t *)bucketsB,
-                     (const unsigned long long *)keysB, N, (const int2 *)plan, (const int32_t *)exc, (const int32_t *)excRank,
-                     (const int32_t *)consumes, (const int32_t *)blockRank, dst->live.visType, dst->freeview.visType, res);
-  hipLaunchKernelGGL(k_merge_finish, dim3(1), dim3(64), 0, dst->stream, dst->scene, res);
+  hipLaunchKernelGGL(k_merge_plan, g, dim3(256), 0, dst->stream, m, dst->scene, (const uint32_t *)s.bucketsB, N, s.plan, s.exc, s.res);
+  b = s.tmpBytes; HIP_TRY(hipcub::DeviceScan::ExclusiveSum(s.tmp, b, s.exc, s.excRank, N, dst->stream));
+  hipLaunchKernelGGL(k_merge_consume, g, dim3(256), 0, dst->stream, (const uint32_t *)s.bucketsB, N, (const int32_t *)s.exc,
+                     (const int32_t *)s.excRank, (const int32_t *)s.res, s.consumes);
+  b = s.tmpBytes; HIP_TRY(hipcub::DeviceScan::ExclusiveSum(s.tmp, b, s.consumes, s.blockRank, N, dst->stream));
+  hipLaunchKernelGGL(k_merge_apply, g, dim3(256), 0, dst->stream, m, dst->scene, (const uint32_t *)s.bucketsB,
+                     (const unsigned long long *)s.keysB, N, (const int2 *)s.plan, (const int32_t *)s.exc, (const int32_t *)s.excRank,
+                     (const int32_t *)s.consumes, (const int32_t *)s.blockRank, dst->live.visType, dst->freeview.visType, s.res);
+  hipLaunchKernelGGL(k_merge_finish, dim3(1), dim3(64), 0, dst->stream, dst->scene, s.res);
+  return DSR_OK;
+}
+
+// The tail of such a call, after its last launch: e's map has changed — the free-view cache and the cached list of allocated
+// entries are stale —; then the ONE host wait, for the result words and the voxel count.
+struct InsertOutcome { int32_t res[MR_COUNT]; unsigned long long voxels; int dropped; };
+int insert_read_back(dsr_engine *e, const InsertScratch &s, InsertOutcome &o) {
+  HIP_TRY(hipGetLastError());
+  e->sceneVersion++;
+  e->allocListVersion = ~0ull;
+  e->fvValid = false;
+  HIP_TRY(hipMemcpyAsync(o.res, s.res, sizeof o.res, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(&o.voxels, s.voxels, sizeof o.voxels, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  o.dropped = o.res[MR_NEEDED] - o.res[MR_ALLOCATED];
   return DSR_OK;
 }
 
@@ -68,11 +114,7 @@ void dsr_merge_default_params(dsr_merge_params *p) {
 
 int dsr_merge_volume(dsr_engine *dst, dsr_engine *src, const float src_to_dst_m[16], const dsr_merge_params *params,
                      dsr_merge_result *result) {
-  if (!dst || !src || !src_to_dst_m) return fail(DSR_E_ARG, "merge: null argument");
-  if (dst == src) return fail(DSR_E_ARG, "merge: dst and src are the same engine");
-  if (dst->device != src->device) return fail(DSR_E_ARG, "merge: the engines sit on different devices (move one with dsr_snapshot_export / _import)");
-  if (dst->s.use_swapping || src->s.use_swapping) return fail(DSR_E_ARG, "merge: engines with use_swapping are not supported");
-  if (!rigid_transform(src_to_dst_m)) return fail(DSR_E_ARG, "merge: src_to_dst is not a rigid transform");
+  if (int st = two_volume_check(dst, src, src_to_dst_m, "merge", "src_to_dst")) return st;
   dsr_merge_params prm;
   dsr_merge_default_params(&prm);
   if (params) prm = *params;
@@ -103,72 +145,42 @@ int dsr_merge_volume(dsr_engine *dst, dsr_engine *src, const float src_to_dst_m[
   CHECK_E(src);
   CHECK_E(dst);
 
-  Scratch sc("merge: out of device memory for the candidate lists");
-  unsigned long long *keysA, *keysB, *voxels;
-  uint32_t *bucketsA, *bucketsB;
-  int32_t *info, *exc, *excRank, *consumes, *blockRank, *res, *nUnique;
-  int2 *plan;
+  InsertScratch s("merge: out of device memory for the candidate lists");
   int st;
-  if ((st = sc.get(&keysA, N)) || (st = sc.get(&keysB, N)) || (st = sc.get(&bucketsA, N)) || (st = sc.get(&bucketsB, N)) ||
-      (st = sc.get(&info, N)) || (st = sc.get(&exc, N)) || (st = sc.get(&excRank, N)) || (st = sc.get(&consumes, N)) ||
-      (st = sc.get(&blockRank, N)) || (st = sc.get(&plan, N)) || (st = sc.get(&res, MR_COUNT + 1)) || (st = sc.get(&voxels, 1)))
-    return st;
-  nUnique = res + MR_COUNT;
-  size_t tmpBytes = 0, b = 0;
-  HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, b, keysA, keysB, N, 0, 49, dst->stream)); tmpBytes = std::max(tmpBytes, b);
-  HIP_TRY(hipcub::DeviceSelect::Unique(nullptr, b, keysB, keysA, nUnique, N, dst->stream)); tmpBytes = std::max(tmpBytes, b);
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, b, bucketsA, bucketsB, keysA, keysB, N, 0, 32, dst->stream)); tmpBytes = std::max(tmpBytes, b);
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, b, exc, excRank, N, dst->stream)); tmpBytes = std::max(tmpBytes, b);
-  uint8_t *tmp;
-  if ((st = sc.get(&tmp, tmpBytes))) return st;
-
-  // src's queued work before the first read of it (as dsr_stream_wait_for_engine orders a foreign stream)
-  if (src->stream != dst->stream) {
-    if (!src->orderEvent) HIP_TRY(hipEventCreateWithFlags(&src->orderEvent, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(src->orderEvent, src->stream));
-    HIP_TRY(hipStreamWaitEvent(dst->stream, src->orderEvent, 0));
-  }
-  HIP_TRY(hipMemsetAsync(voxels, 0, sizeof *voxels, dst->stream));
+  if ((st = s.init(N, true, dst->stream)) || (st = order_after(dst, src))) return st;
+  unsigned long long *const keysA = s.keysA, *const keysB = s.keysB;
+  int32_t *const res = s.res, *const nUnique = s.nUnique;
 
   const int gridN = std::min(div_up(N, 256), 4096);
   LAUNCH(dst, "merge_enumerate", k_merge_fill, dim3(gridN), dim3(256), keysA, N, res);
   LAUNCH(dst, "merge_enumerate", k_merge_enumerate, dim3(std::min(div_up(src->E, 256), 4096)), dim3(256), m, src->scene, keysA, res);
   {
     ProfScope ps(dst, "merge_sort");
-    b = tmpBytes; HIP_TRY(hipcub::DeviceRadixSort::SortKeys(tmp, b, keysA, keysB, N, 0, 49, dst->stream));
-    b = tmpBytes; HIP_TRY(hipcub::DeviceSelect::Unique(tmp, b, keysB, keysA, nUnique, N, dst->stream));
+    size_t b = s.tmpBytes; HIP_TRY(hipcub::DeviceRadixSort::SortKeys(s.tmp, b, keysA, keysB, N, 0, 49, dst->stream));
+    b = s.tmpBytes; HIP_TRY(hipcub::DeviceSelect::Unique(s.tmp, b, keysB, keysA, nUnique, N, dst->stream));
   }
   // keysA[0 .. *nUnique): the distinct candidates (and the one fill value, last); info / bucketsA beyond them: "nothing"
-  HIP_TRY(hipMemsetAsync(bucketsA, 0xff, (size_t)N * sizeof(uint32_t), dst->stream));
-  HIP_TRY(hipMemsetAsync(info, 0xfe, (size_t)N * sizeof(int32_t), dst->stream));  // (< -1)
+  HIP_TRY(hipMemsetAsync(s.bucketsA, 0xff, (size_t)N * sizeof(uint32_t), dst->stream));
+  HIP_TRY(hipMemsetAsync(s.info, 0xfe, (size_t)N * sizeof(int32_t), dst->stream));  // (< -1)
   const int gridChunk = std::min(div_up(chunk, 4), 8192);
   for (int first = 0; first < N; first += chunk)
     LAUNCH(dst, "merge_has_data", k_merge_has_data, dim3(gridChunk), dim3(256), m, src->scene, dst->scene, (const unsigned long long *)keysA,
-           (const int32_t *)nUnique, first, chunk, info, bucketsA, res);
-  if ((st = ordered_insert(dst, m, N, bucketsA, bucketsB, keysA, keysB, plan, exc, excRank, consumes, blockRank, res, tmp, tmpBytes))) return st;
+           (const int32_t *)nUnique, first, chunk, s.info, s.bucketsA, res);
+  if ((st = ordered_insert(dst, m, N, s))) return st;
   for (int first = 0; first < N; first += chunk)
     LAUNCH(dst, "merge_pull", k_merge_pull, dim3(gridChunk), dim3(256), m, src->scene, dst->scene, (const unsigned long long *)keysA,
-           (const int32_t *)nUnique, first, chunk, (const int32_t *)info, voxels);
-  HIP_TRY(hipGetLastError());
-
-  // dst's map has changed: the free-view cache and the cached list of allocated entries are stale
-  dst->sceneVersion++;
-  dst->allocListVersion = ~0ull;
-  dst->fvValid = false;
-
-  int32_t hres[MR_COUNT];
-  unsigned long long hvox = 0;
-  HIP_TRY(hipMemcpyAsync(hres, res, sizeof hres, hipMemcpyDeviceToHost, dst->stream));
-  HIP_TRY(hipMemcpyAsync(&hvox, voxels, sizeof hvox, hipMemcpyDeviceToHost, dst->stream));
-  HIP_TRY(hipStreamSynchronize(dst->stream));  // the one host wait
-  const int dropped = hres[MR_NEEDED] - hres[MR_ALLOCATED];
+           (const int32_t *)nUnique, first, chunk, (const int32_t *)s.info, s.voxels);
+  InsertOutcome o;
+  if ((st = insert_read_back(dst, s, o))) return st;
+  const int32_t *hres = o.res;
+  const int dropped = o.dropped;
   if (result) {
     memset(result, 0, sizeof *result);
     result->candidate_blocks = hres[MR_CANDIDATES];
     result->blocks_with_data = hres[MR_WITH_DATA];
     result->blocks_allocated = hres[MR_ALLOCATED];
     result->blocks_dropped = dropped;
-    result->voxels_updated = (int64_t)hvox;
+    result->voxels_updated = (int64_t)o.voxels;
   }
   if (dropped > 0) return fail(DSR_E_OUT_OF_BLOCKS, "merge: dst ran out of voxel blocks / excess list entries; " + std::to_string(dropped) + " blocks dropped");
   return DSR_OK;
@@ -239,7 +251,7 @@ int dense_import_setup(dsr_engine *e, const dsr_dense_grid *grid, DenseCall &c, 
     const float cx = (float)((k & 1) ? g.nx : -1) * grid->pitch, cy = (float)((k & 2) ? g.ny : -1) * grid->pitch,
                 cz = (float)((k & 4) ? g.nz : -1) * grid->pitch;
     const float3 q = mat_mul3(g2w, cx, cy, cz, 1.0f);
-    const int v[3] = {(int)floorf(merge_clamp(q.x / vs)), (int)floorf(merge_clamp(q.y / vs)), (int)floorf(merge_clamp(q.z / vs))};
+    const int v[3] = {(int)floorf(lattice_clamp(q.x / vs)), (int)floorf(lattice_clamp(q.y / vs)), (int)floorf(lattice_clamp(q.z / vs))};
     for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], v[a]); hi[a] = std::max(hi[a], v[a]); }
   }
   double cap = 1.0;
@@ -264,48 +276,25 @@ int dense_import_run(dsr_engine *e, const DenseCall &c, int N, const float *sdf,
   const DenseP &g = c.g;
   MergeP m{};  // what the ordered insert reads: the dst fields
   m.dstBuckets = e->noBuckets; m.dstEntries = e->E; m.dstBlocks = e->noBlocks; m.dstMask = g.mask;
-  Scratch sc("dense import: out of device memory for the candidate lists");
-  unsigned long long *keysA, *keysB, *voxels;
-  uint32_t *bucketsA, *bucketsB;
-  int32_t *info, *exc, *excRank, *consumes, *blockRank, *res;
-  int2 *plan;
+  InsertScratch s("dense import: out of device memory for the candidate lists");
   int st;
-  if ((st = sc.get(&keysA, N)) || (st = sc.get(&keysB, N)) || (st = sc.get(&bucketsA, N)) || (st = sc.get(&bucketsB, N)) ||
-      (st = sc.get(&info, N)) || (st = sc.get(&exc, N)) || (st = sc.get(&excRank, N)) || (st = sc.get(&consumes, N)) ||
-      (st = sc.get(&blockRank, N)) || (st = sc.get(&plan, N)) || (st = sc.get(&res, MR_COUNT)) || (st = sc.get(&voxels, 1)))
-    return st;
-  size_t tmpBytes = 0, b = 0;
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, b, bucketsA, bucketsB, keysA, keysB, N, 0, 32, e->stream)); tmpBytes = std::max(tmpBytes, b);
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, b, exc, excRank, N, e->stream)); tmpBytes = std::max(tmpBytes, b);
-  uint8_t *tmp;
-  if ((st = sc.get(&tmp, tmpBytes))) return st;
-
-  HIP_TRY(hipMemsetAsync(voxels, 0, sizeof *voxels, e->stream));
-  LAUNCH(e, "dense_import", k_dense_candidates, dim3(std::min(div_up(N, 256), 4096)), dim3(256), g, keysA, N, res);
+  if ((st = s.init(N, false, e->stream))) return st;
+  LAUNCH(e, "dense_import", k_dense_candidates, dim3(std::min(div_up(N, 256), 4096)), dim3(256), g, s.keysA, N, s.res);
   const int gridW = std::min(div_up(N, 4), 8192);
-  LAUNCH(e, "dense_import", k_dense_has_data, dim3(gridW), dim3(256), g, e->scene, sdf, wd, N, info, bucketsA, res);
-  if ((st = ordered_insert(e, m, N, bucketsA, bucketsB, keysA, keysB, plan, exc, excRank, consumes, blockRank, res, tmp, tmpBytes))) return st;
+  LAUNCH(e, "dense_import", k_dense_has_data, dim3(gridW), dim3(256), g, e->scene, sdf, wd, N, s.info, s.bucketsA, s.res);
+  if ((st = ordered_insert(e, m, N, s))) return st;
   LAUNCH(e, "dense_import", k_dense_pull, dim3(gridW), dim3(256), g, e->scene, sdf, wd, reinterpret_cast<const uint32_t *>(rgba), N,
-         (const int32_t *)info, voxels);
-  HIP_TRY(hipGetLastError());
-
-  // the map has changed: the free-view cache and the cached list of allocated entries are stale
-  e->sceneVersion++;
-  e->allocListVersion = ~0ull;
-  e->fvValid = false;
-
-  int32_t hres[MR_COUNT];
-  unsigned long long hvox = 0;
-  HIP_TRY(hipMemcpyAsync(hres, res, sizeof hres, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(&hvox, voxels, sizeof hvox, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));  // the one host wait
-  const int dropped = hres[MR_NEEDED] - hres[MR_ALLOCATED];
+         (const int32_t *)s.info, s.voxels);
+  InsertOutcome o;
+  if ((st = insert_read_back(e, s, o))) return st;
+  const int32_t *hres = o.res;
+  const int dropped = o.dropped;
   if (result) {
     result->candidate_blocks = N;
     result->blocks_with_data = hres[MR_WITH_DATA];
     result->blocks_allocated = hres[MR_ALLOCATED];
     result->blocks_dropped = dropped;
-    result->voxels_updated = (int64_t)hvox;
+    result->voxels_updated = (int64_t)o.voxels;
   }
   if (dropped > 0) return fail(DSR_E_OUT_OF_BLOCKS, "dense import: the engine ran out of voxel blocks / excess list entries; " + std::to_string(dropped) + " blocks dropped");
   return DSR_OK;

@@ -9,16 +9,16 @@
 // weight plane it owns), its 8 voxels summed pairwise; the 64 lane sums by the xor butterfly; the block partials, in the order of
 // the ascending list of allocated entries, by the stride-doubling tree.  tests/alignref/align_ref.cpp restates it on the CPU.
 // The step, level_begin and the tree are the tracker's (k_track.h, which belongs to dsr_track.hip), restated here with what
-// differs — f, the too-few-pairs rule, the delta applied to T itself: a kernel header belongs to exactly one translation unit.
+// differs — f, the too-few-pairs rule, the delta applied to T itself.  Reading dst — the chain walk, the box of blocks in LDS, the
+// corner gather, the trilinear expression order — is shared (dsr_sample.h).
 #pragma once
-#include "dsr_device.h"
 #include "dsr_math.h"
+#include "dsr_sample.h"
 
 namespace dsr {
 
 constexpr int kAlignVals = 28;  // b b, b A[6], the lower triangle of A A^T [21]
 constexpr int kAlignStepThreads = 1024;
-constexpr float kAlignClamp = 3.0e5f;  // beyond every int16 block's voxels; keeps float -> int defined
 
 struct AlignP {
   float vsSrc, vsDst, muSrc, muDst;
@@ -70,95 +70,39 @@ struct AlignIsAllocated {
   __host__ __device__ __forceinline__ bool operator()(const int &i) const { return table[i].ptr >= 0; }
 };
 
-__host__ __device__ __forceinline__ float align_clamp(float v) { return fminf(fmaxf(v, -kAlignClamp), kAlignClamp); }
-
-// findVoxel's chain walk in dst: the block pointer of (bx, by, bz), or -1
-__device__ __forceinline__ int align_find_block(const dsr_hash_entry *__restrict__ table, int noBuckets, uint32_t mask, int bx, int by, int bz) {
-  uint32_t idx = hash_index(bx, by, bz, mask);
-  while (true) {
-    const dsr_hash_entry he = load_entry(table, idx);
-    if (he.pos[0] == bx && he.pos[1] == by && he.pos[2] == bz && he.ptr >= 0) return he.ptr;
-    if (he.offset < 1) break;
-    idx = (uint32_t)(noBuckets + he.offset - 1);
-  }
-  return -1;
-}
-
 // position of src lattice point (x, y, z): q in dst metres, u in dst voxels (dsr_align.h step 1)
 __device__ __forceinline__ void align_dst_pos(const AlignP &a, const Mat4 &T, int x, int y, int z, float3 &q, float3 &u) {
   q = mat_mul3(T, (float)x * a.vsSrc, (float)y * a.vsSrc, (float)z * a.vsSrc, 1.0f);
-  u = make_float3(align_clamp(q.x / a.vsDst), align_clamp(q.y / a.vsDst), align_clamp(q.z / a.vsDst));
+  u = make_float3(lattice_clamp(q.x / a.vsDst), lattice_clamp(q.y / a.vsDst), lattice_clamp(q.z / a.vsDst));
 }
 
-// The dst blocks one wave's src block reaches into, resolved once per wave into LDS: a box of up to 4 x 4 x 4 dst blocks (one per
-// lane) — k_merge.h's merge_resolve_box with the roles swapped.  A block outside the box is found through the lane's own cache.
-struct AlignBox { int x0, y0, z0; bool on; };
-struct AlignVoxCache { int bx, by, bz, ptr; };
-
-__device__ __forceinline__ AlignBox align_resolve_box(const AlignP &a, const Mat4 &T, const SceneP &dst, int bx, int by, int bz, int *boxPtr,
+// the dst blocks one wave's src block reaches into (all lanes of the wave; dsr_sample.h box_resolve)
+__device__ __forceinline__ BlockBox align_resolve_box(const AlignP &a, const Mat4 &T, const VolumeP &dst, int bx, int by, int bz, int *boxPtr,
                                                       int lane) {
-  float lo[3] = {kAlignClamp, kAlignClamp, kAlignClamp}, hi[3] = {-kAlignClamp, -kAlignClamp, -kAlignClamp};
+  float lo[3], hi[3];
+  bounds_init(lo, hi);
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
     float3 q, u;
     align_dst_pos(a, T, bx * 8 + ((c & 1) ? 7 : 0), by * 8 + ((c & 2) ? 7 : 0), bz * 8 + ((c & 4) ? 7 : 0), q, u);
-    lo[0] = fminf(lo[0], u.x); lo[1] = fminf(lo[1], u.y); lo[2] = fminf(lo[2], u.z);
-    hi[0] = fmaxf(hi[0], u.x); hi[1] = fmaxf(hi[1], u.y); hi[2] = fmaxf(hi[2], u.z);
+    bounds_add(lo, hi, u);
   }
-  AlignBox box;
-  // (the clamp maps a NaN to -3e5, so the casts are defined; a voxel outside the box goes through the lane's cache: no result
-  // depends on the box)
-  box.x0 = ((int)floorf(lo[0]) - 1) >> 3; box.y0 = ((int)floorf(lo[1]) - 1) >> 3; box.z0 = ((int)floorf(lo[2]) - 1) >> 3;
-  box.on = (((int)floorf(hi[0]) + 2) >> 3) - box.x0 < 4 && (((int)floorf(hi[1]) + 2) >> 3) - box.y0 < 4 &&
-           (((int)floorf(hi[2]) + 2) >> 3) - box.z0 < 4;
-  int ptr = -1;
-  if (box.on) ptr = align_find_block(dst.table, a.dstBuckets, a.dstMask, box.x0 + (lane & 3), box.y0 + ((lane >> 2) & 3), box.z0 + (lane >> 4));
-  boxPtr[lane] = ptr;  // (read by this wave only: the wave's own LDS slice, no barrier needed beyond the wave's lockstep)
-  __builtin_amdgcn_wave_barrier();
-  return box;
-}
-
-__device__ __forceinline__ int align_dst_block(const AlignP &a, const SceneP &dst, const AlignBox &box, const int *__restrict__ boxPtr,
-                                               AlignVoxCache &cache, int bx, int by, int bz) {
-  const uint32_t ux = (uint32_t)(bx - box.x0), uy = (uint32_t)(by - box.y0), uz = (uint32_t)(bz - box.z0);
-  if (box.on && ux < 4u && uy < 4u && uz < 4u) return boxPtr[ux + 4u * uy + 16u * uz];
-  if (bx == cache.bx && by == cache.by && bz == cache.bz) return cache.ptr;
-  const int ptr = align_find_block(dst.table, a.dstBuckets, a.dstMask, bx, by, bz);
-  cache.bx = bx; cache.by = by; cache.bz = bz; cache.ptr = ptr;
-  return ptr;
+  return box_resolve(dst, lo, hi, boxPtr, lane);
 }
 
 // one src voxel (lattice x, y, z; raw sdf, weight): the 28 values of its pair, or false (v untouched)
-__device__ __forceinline__ bool align_pair(const AlignP &a, const Mat4 &T, const SceneP &dst, const AlignBox &box,
-                                           const int *__restrict__ boxPtr, AlignVoxCache &cache, int x, int y, int z, short raw, int w,
+__device__ __forceinline__ bool align_pair(const AlignP &a, const Mat4 &T, const VolumeP &dst, const BlockBox &box,
+                                           const int *__restrict__ boxPtr, BlockCache &cache, int x, int y, int z, short raw, int w,
                                            float *v) {
   if (w < a.minW || raw >= 32767 || raw <= -32767) return false;
   float3 q, u;
   align_dst_pos(a, T, x, y, z, q, u);
-  const float flx = floorf(u.x), fly = floorf(u.y), flz = floorf(u.z);
-  const int ix = (int)flx, iy = (int)fly, iz = (int)flz;
-  const float fx = u.x - flx, fy = u.y - fly, fz = u.z - flz;
-  float c[8];
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    c[k] = 0.0f;
-    if (!ok) continue;
-    const int cx = ix + (k & 1), cy = iy + ((k >> 1) & 1), cz = iz + (k >> 2);
-    const int ptr = align_dst_block(a, dst, box, boxPtr, cache, cx >> 3, cy >> 3, cz >> 3);
-    if (ptr < 0) { ok = false; continue; }
-    const uint8_t *blk = dst.vba + (size_t)ptr * kBlockBytes;
-    const int lin = (cx & 7) + ((cy & 7) << 3) + ((cz & 7) << 6);
-    if ((int)blk[kOffWDepth + lin] < a.minW) { ok = false; continue; }
-    c[k] = (float)*reinterpret_cast<const short *>(blk + kOffSdf + lin * 2);
-  }
-  if (!ok) return false;
-  // readFromSDF_float_interpolated's expression order (k_merge.h merge_sample)
-  float res1 = (1.0f - fx) * c[0] + fx * c[1];
-  res1 = (1.0f - fy) * res1 + fy * ((1.0f - fx) * c[2] + fx * c[3]);
-  float res2 = (1.0f - fx) * c[4] + fx * c[5];
-  res2 = (1.0f - fy) * res2 + fy * ((1.0f - fx) * c[6] + fx * c[7]);
-  const float dRaw = (1.0f - fz) * res1 + fz * res2;
+  const LatticeCell cell = lattice_cell(u);
+  const float fx = cell.cx, fy = cell.cy, fz = cell.cz;
+  Corners corners;  // all eight: the gradient needs the corners of weight 0 too
+  if (!gather_corners(dst, box, boxPtr, cache, cell, GATHER_ALL, a.minW, corners)) return false;
+  const float *c = corners.v;
+  const float dRaw = trilinear8(c, fx, fy, fz);
   const float gx = (1.0f - fz) * ((1.0f - fy) * (c[1] - c[0]) + fy * (c[3] - c[2])) + fz * ((1.0f - fy) * (c[5] - c[4]) + fy * (c[7] - c[6]));
   const float gy = (1.0f - fz) * ((1.0f - fx) * (c[2] - c[0]) + fx * (c[3] - c[1])) + fz * ((1.0f - fx) * (c[6] - c[4]) + fx * (c[7] - c[5]));
   const float gz = (1.0f - fy) * ((1.0f - fx) * (c[4] - c[0]) + fx * (c[5] - c[1])) + fy * ((1.0f - fx) * (c[6] - c[2]) + fx * (c[7] - c[3]));
@@ -194,6 +138,7 @@ __global__ __launch_bounds__(256) void k_align_gh(AlignP a, SceneP src, SceneP d
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   int *boxPtr = boxPtrAll[wave];
+  const VolumeP dstVol{dst.table, dst.vba, a.dstBuckets, a.dstMask};
   Mat4 T;
   align_load_pose(st->T, T);
   const int n = min(*nListPtr, a.ld);
@@ -202,9 +147,8 @@ __global__ __launch_bounds__(256) void k_align_gh(AlignP a, SceneP src, SceneP d
   for (int i = blockIdx.x * 4 + wave; i < n; i += gridDim.x * 4) {
     const dsr_hash_entry he = load_entry(src.table, (uint32_t)list[i]);
     const int bx = he.pos[0], by = he.pos[1], bz = he.pos[2];
-    __builtin_amdgcn_wave_barrier();
-    const AlignBox box = align_resolve_box(a, T, dst, bx, by, bz, boxPtr, lane);
-    AlignVoxCache cache; cache.bx = cache.by = cache.bz = 0x7fffffff; cache.ptr = -1;
+    const BlockBox box = align_resolve_box(a, T, dstVol, bx, by, bz, boxPtr, lane);
+    BlockCache cache = block_cache_empty();
     const uint8_t *blk = src.vba + (size_t)he.ptr * kBlockBytes;
     const uint4 sdfRow = *reinterpret_cast<const uint4 *>(blk + kOffSdf + lane * 16);
     const uint2 wRow = *reinterpret_cast<const uint2 *>(blk + kOffWDepth + lane * 8);
@@ -222,7 +166,7 @@ __global__ __launch_bounds__(256) void k_align_gh(AlignP a, SceneP src, SceneP d
       if (rowOn && (x & (stride - 1)) == 0) {
         const short raw = (short)(unsigned short)((x < 4 ? sdfLo : sdfHi) >> ((x & 3) * 16));
         const int w = (int)((w8 >> (x * 8)) & 0xffu);
-        ok = align_pair(a, T, dst, box, boxPtr, cache, bx * 8 + x, by * 8 + y, bz * 8 + z, raw, w, v);
+        ok = align_pair(a, T, dstVol, box, boxPtr, cache, bx * 8 + x, by * 8 + y, bz * 8 + z, raw, w, v);
       }
       if (!ok) {
 #pragma unroll

@@ -7,17 +7,17 @@
 //   k_merge_plan / _consume / _apply   the ordered insert of the candidates dst lacks (bucket by bucket, ranks from scans);
 //   k_merge_pull        the hot path: one wave per dst block, 8 voxels per lane in the plane-wise layout.
 // merge_sample below is the per-voxel definition both the has-data and the pull pass evaluate; tests/mergeref/merge_ref.cpp
-// restates it serially.  The few device functions of k_raycast.h / k_swap.h it needs (chain walk, trilinear expression order,
-// combineVoxel*Information) are restated here: a kernel header belongs to exactly one translation unit (dsr_internal.h).
+// restates it serially.  The chain walk, the box of blocks in LDS, the corner gather and the trilinear expression order are
+// shared (dsr_sample.h), combineVoxel*Information too (dsr_device.h).  The has-data and the pull pass are written once, over a
+// SOURCE of samples: the volume here, a dense grid's planes in k_dense.h.
 #pragma once
-#include "dsr_device.h"
+#include "dsr_sample.h"
 
 namespace dsr {
 
 constexpr unsigned long long kMergeNoKey = 1ull << 48;   // sorts behind every packed position
 constexpr unsigned long long kMergeKeyMask = (1ull << 48) - 1;
 constexpr uint32_t kMergeNoBucket = 0xffffffffu;
-constexpr float kMergeClamp = 3.0e5f;                    // beyond every int16 block's voxels; keeps float -> int defined
 
 enum MergeRes {  // the device-side result words
   MR_CANDIDATES = 0, MR_WITH_DATA = 1, MR_ALLOCATED = 2, MR_NEEDED = 3, MR_ALLOCATED_EXCESS = 4, MR_SRC_ENTRIES = 5, MR_UNIQUE = 6,
@@ -46,22 +46,6 @@ __host__ __device__ __forceinline__ void merge_unkey(unsigned long long key, int
   bx = (int)(packed & 0xffffu) - 32768; by = (int)((packed >> 16) & 0xffffu) - 32768; bz = (int)((packed >> 32) & 0xffffu) - 32768;
 }
 
-__host__ __device__ __forceinline__ float merge_clamp(float v) { return fminf(fmaxf(v, -kMergeClamp), kMergeClamp); }
-
-// findVoxel's chain walk: the entry that holds block (bx, by, bz) with ptr >= 0, or -1
-__device__ __forceinline__ int merge_find_entry(const dsr_hash_entry *__restrict__ table, int noBuckets, uint32_t mask, int bx, int by,
-                                                int bz, int &ptr) {
-  uint32_t idx = hash_index(bx, by, bz, mask);
-  while (true) {
-    const dsr_hash_entry he = load_entry(table, idx);
-    if (he.pos[0] == bx && he.pos[1] == by && he.pos[2] == bz && he.ptr >= 0) { ptr = he.ptr; return (int)idx; }
-    if (he.offset < 1) break;
-    idx = (uint32_t)(noBuckets + he.offset - 1);
-  }
-  ptr = -1;
-  return -1;
-}
-
 // ------------------------------------------------------------------ candidates
 
 __global__ __launch_bounds__(256) void k_merge_fill(unsigned long long *__restrict__ keys, int n, int32_t *__restrict__ res) {
@@ -85,7 +69,7 @@ __global__ __launch_bounds__(256) void k_merge_enumerate(MergeP m, SceneP src, u
       const float cy = (float)(he.pos[1] * 8 + ((c & 2) ? 8 : -1)) * m.vsSrc;
       const float cz = (float)(he.pos[2] * 8 + ((c & 4) ? 8 : -1)) * m.vsSrc;
       const float3 q = mat_mul3(m.srcToDst, cx, cy, cz, 1.0f);
-      const int v[3] = {(int)floorf(merge_clamp(q.x / m.vsDst)), (int)floorf(merge_clamp(q.y / m.vsDst)), (int)floorf(merge_clamp(q.z / m.vsDst))};
+      const int v[3] = {(int)floorf(lattice_clamp(q.x / m.vsDst)), (int)floorf(lattice_clamp(q.y / m.vsDst)), (int)floorf(lattice_clamp(q.z / m.vsDst))};
 #pragma unroll
       for (int a = 0; a < 3; ++a) { lo[a] = v[a] < lo[a] ? v[a] : lo[a]; hi[a] = v[a] > hi[a] ? v[a] : hi[a]; }
     }
@@ -110,166 +94,97 @@ __global__ __launch_bounds__(256) void k_merge_enumerate(MergeP m, SceneP src, u
 
 // ------------------------------------------------------------------ the pull of one voxel
 
-// the src blocks one wave's dst block reaches into, resolved once per wave into LDS: a box of up to 4 x 4 x 4 src blocks (one
-// per lane).  A block outside the box (none when the grids are of similar pitch) is found through the lane's own VoxCache.
-struct MergeBox { int x0, y0, z0; bool on; };
-struct MergeVoxCache { int bx, by, bz, ptr; };
+struct MergeSample { bool valid; short g; int w; uchar4 clr; };  // g, w, clr: read only where valid
 
-__device__ __forceinline__ int merge_src_block(const MergeP &m, const SceneP &src, const MergeBox &box, const int *__restrict__ boxPtr,
-                                               MergeVoxCache &cache, int bx, int by, int bz) {
-  const uint32_t ux = (uint32_t)(bx - box.x0), uy = (uint32_t)(by - box.y0), uz = (uint32_t)(bz - box.z0);
-  if (box.on && ux < 4u && uy < 4u && uz < 4u) return boxPtr[ux + 4u * uy + 16u * uz];
-  if (bx == cache.bx && by == cache.by && bz == cache.bz) return cache.ptr;
-  int ptr;
-  merge_find_entry(src.table, m.srcBuckets, m.srcMask, bx, by, bz, ptr);
-  cache.bx = bx; cache.by = by; cache.bz = bz; cache.ptr = ptr;
-  return ptr;
-}
+// What dst's voxels are pulled FROM.  A source answers: candidate(i, b): the block position of candidate i, or false — nothing
+// there; prepare(b): all lanes of the wave, before its voxels of block b are sampled; sample(x, y, z): dst voxel (x, y, z).
+// This one is the merge's: the unique keys, src sampled through the box of src blocks in the wave's 64 words of LDS.
+struct MergeVolumeSource {
+  const MergeP &m;
+  VolumeP vol;
+  const unsigned long long *__restrict__ cand;
+  int *boxPtr;
+  int lane;
+  BlockBox box;
+  BlockCache cache;
 
-// position of dst lattice point (dx, dy, dz) in src voxel units (dsr_merge.h step 1)
-__device__ __forceinline__ float3 merge_src_pos(const MergeP &m, int dx, int dy, int dz) {
-  const Mat4 &a = m.dstToSrc;
-  const float x = (float)dx, y = (float)dy, z = (float)dz;
-  return make_float3(merge_clamp((a.m[0] * x + a.m[4] * y + a.m[8] * z) * m.scale + m.tx),
-                     merge_clamp((a.m[1] * x + a.m[5] * y + a.m[9] * z) * m.scale + m.ty),
-                     merge_clamp((a.m[2] * x + a.m[6] * y + a.m[10] * z) * m.scale + m.tz));
-}
-
-// all lanes of the wave: the box of dst block (bx, by, bz) and its block pointers
-__device__ __forceinline__ MergeBox merge_resolve_box(const MergeP &m, const SceneP &src, int bx, int by, int bz, int *boxPtr, int lane) {
-  float lo[3] = {kMergeClamp, kMergeClamp, kMergeClamp}, hi[3] = {-kMergeClamp, -kMergeClamp, -kMergeClamp};
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const float3 p = merge_src_pos(m, bx * 8 + ((c & 1) ? 7 : 0), by * 8 + ((c & 2) ? 7 : 0), bz * 8 + ((c & 4) ? 7 : 0));
-    lo[0] = fminf(lo[0], p.x); lo[1] = fminf(lo[1], p.y); lo[2] = fminf(lo[2], p.z);
-    hi[0] = fmaxf(hi[0], p.x); hi[1] = fmaxf(hi[1], p.y); hi[2] = fmaxf(hi[2], p.z);
+  __device__ __forceinline__ bool candidate(long long i, int b[3]) const {
+    const unsigned long long key = cand[i];
+    if (key == kMergeNoKey) return false;  // the one sentinel the de-duplication leaves
+    merge_unkey(key, b[0], b[1], b[2]);
+    return true;
   }
-  MergeBox box;
-  box.x0 = ((int)floorf(lo[0]) - 1) >> 3; box.y0 = ((int)floorf(lo[1]) - 1) >> 3; box.z0 = ((int)floorf(lo[2]) - 1) >> 3;
-  box.on = (((int)floorf(hi[0]) + 2) >> 3) - box.x0 < 4 && (((int)floorf(hi[1]) + 2) >> 3) - box.y0 < 4 &&
-           (((int)floorf(hi[2]) + 2) >> 3) - box.z0 < 4;
-  int ptr = -1;
-  if (box.on) merge_find_entry(src.table, m.srcBuckets, m.srcMask, box.x0 + (lane & 3), box.y0 + ((lane >> 2) & 3), box.z0 + (lane >> 4), ptr);
-  boxPtr[lane] = ptr;  // (read by this wave only: the wave's own LDS slice, no barrier needed beyond the wave's lockstep)
-  __builtin_amdgcn_wave_barrier();
-  return box;
-}
-
-struct MergeSample { bool valid; short g; int w; uchar4 clr; };
-
-__device__ __forceinline__ MergeSample merge_sample(const MergeP &m, const SceneP &src, const MergeBox &box, const int *__restrict__ boxPtr,
-                                                    MergeVoxCache &cache, int dx, int dy, int dz) {
-  MergeSample r; r.valid = false; r.g = 0; r.w = 0; r.clr = make_uchar4(0, 0, 0, 0);
-  const float3 p = merge_src_pos(m, dx, dy, dz);
-  const float flx = floorf(p.x), fly = floorf(p.y), flz = floorf(p.z);
-  const int ix = (int)flx, iy = (int)fly, iz = (int)flz;
-  const float cx = p.x - flx, cy = p.y - fly, cz = p.z - flz;
-  const float wx[2] = {1.0f - cx, cx}, wy[2] = {1.0f - cy, cy}, wz[2] = {1.0f - cz, cz};
-  const int nearest = (cx >= 0.5f ? 1 : 0) | (cy >= 0.5f ? 2 : 0) | (cz >= 0.5f ? 4 : 0);
-  float v[8];
-  bool ok = true;
-  const uint8_t *nearBlk = nullptr;
-  int nearLin = 0;
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const int ox = c & 1, oy = (c >> 1) & 1, oz = c >> 2;
-    v[c] = 0.0f;
-    if (!ok || wx[ox] == 0.0f || wy[oy] == 0.0f || wz[oz] == 0.0f) continue;
-    const int x = ix + ox, y = iy + oy, z = iz + oz;
-    const int ptr = merge_src_block(m, src, box, boxPtr, cache, x >> 3, y >> 3, z >> 3);
-    if (ptr < 0) { ok = false; continue; }
-    const uint8_t *blk = src.vba + (size_t)ptr * kBlockBytes;
-    const int lin = (x & 7) + ((y & 7) << 3) + ((z & 7) << 6);
-    const int w = blk[kOffWDepth + lin];
-    if (w < m.minW) { ok = false; continue; }
-    v[c] = (float)*reinterpret_cast<const short *>(blk + kOffSdf + lin * 2);
-    if (c == nearest) { r.w = w; nearBlk = blk; nearLin = lin; }
+  __device__ __forceinline__ void prepare(const int b[3]) {
+    float lo[3], hi[3];
+    lattice_bounds(m.dstToSrc, m.scale, m.tx, m.ty, m.tz, b[0] * 8, b[1] * 8, b[2] * 8, 7, 7, 7, lo, hi);
+    box = box_resolve(vol, lo, hi, boxPtr, lane);
+    cache = block_cache_empty();
   }
-  if (!ok) return r;
-  // readFromSDF_float_interpolated's expression order (k_raycast.h read_sdf_interpolated_raw)
-  float res1 = (1.0f - cx) * v[0] + cx * v[1];
-  res1 = (1.0f - cy) * res1 + cy * ((1.0f - cx) * v[2] + cx * v[3]);
-  float res2 = (1.0f - cx) * v[4] + cx * v[5];
-  res2 = (1.0f - cy) * res2 + cy * ((1.0f - cx) * v[6] + cx * v[7]);
-  const float sdfS = (1.0f - cz) * res1 + cz * res2;
-  float g = (sdfS / 32767.0f) * m.muRatio;
-  if (g < -1.0f) return r;
-  g = fminf(g, 1.0f);
-  r.g = (short)(int)(g * 32767.0f);
-  r.valid = true;
-  if (m.mergeColour && nearBlk) r.clr =*reinterpret_cast<const uchar4 *>(nearBlk + kOffClr + nearLin * 4);
-  return r;
-}
-
-// ITMSwappingEngine.h combineVoxelDepthInformation / combineVoxelColorInformation (k_swap.h combine_voxel_depth / _colour):
-// (oldSdf, oldW) and sc are the incoming sample, in the role of the stored copy
-__device__ __forceinline__ void merge_combine_depth(short oldSdf, int oldW, int maxW, short &sdf, int &w) {
-  float newF = (float)sdf / 32767.0f;
-  const float oldF = (float)oldSdf / 32767.0f;
-  newF = (float)oldW * oldF + (float)w * newF;
-  w = oldW + w;
-  newF /= (float)w;
-  w = w < maxW ? w : maxW;
-  sdf = (short)(int)(newF * 32767.0f);
-}
-__device__ __forceinline__ uchar4 merge_combine_colour(uchar4 sc, uchar4 dc, int maxW) {
-  int newW = dc.w;
-  const int oldW = sc.w;
-  float nx = (float)dc.x / 255.0f, ny = (float)dc.y / 255.0f, nz = (float)dc.z / 255.0f;
-  const float ox = (float)sc.x / 255.0f, oy = (float)sc.y / 255.0f, oz = (float)sc.z / 255.0f;
-  nx = ox * (float)oldW + nx * (float)newW;
-  ny = oy * (float)oldW + ny * (float)newW;
-  nz = oz * (float)oldW + nz * (float)newW;
-  newW = oldW + newW;
-  nx /= (float)newW; ny /= (float)newW; nz /= (float)newW;
-  newW = newW < maxW ? newW : maxW;
-  return make_uchar4((uint8_t)(int)(nx * 255.0f), (uint8_t)(int)(ny * 255.0f), (uint8_t)(int)(nz * 255.0f), (uint8_t)newW);
-}
+  // dsr_merge.h steps 1-4: position in src voxel units, the corners with weight, the rescaled value, the nearest corner's colour
+  __device__ __forceinline__ MergeSample sample(int dx, int dy, int dz) {
+    MergeSample r; r.valid = false; r.g = 0; r.w = 0; r.clr = make_uchar4(0, 0, 0, 0);
+    const LatticeCell q = lattice_cell(lattice_pos(m.dstToSrc, m.scale, m.tx, m.ty, m.tz, dx, dy, dz));
+    Corners c;
+    if (!gather_corners(vol, box, boxPtr, cache, q, GATHER_WEIGHTED, m.minW, c)) return r;
+    float g = (trilinear8(c.v, q.cx, q.cy, q.cz) / 32767.0f) * m.muRatio;
+    if (g < -1.0f) return r;
+    g = fminf(g, 1.0f);
+    r.g = (short)(int)(g * 32767.0f);
+    r.w = c.nearW;
+    r.valid = true;
+    if (m.mergeColour && c.nearBlk) r.clr = *reinterpret_cast<const uchar4 *>(c.nearBlk + kOffClr + c.nearLin * 4);
+    return r;
+  }
+};
 
 // ------------------------------------------------------------------ has-data pass
 
-// One wave per unique candidate in [first, first + count): info = -2 no voxel gets data; -1 data, not in dst's table;
-// >= 0 data, dst's entry.  For the -1 candidates bucketOut = their bucket (the insert's first sort key), else kMergeNoBucket.
+// One wave per candidate in [first, end): info = -2 no voxel gets data; -1 data, not in dst's table; >= 0 data, dst's entry.
+// For the -1 candidates bucketOut = their bucket (the insert's first sort key), else kMergeNoBucket.  countCandidates: the
+// candidates the source has are counted in res[MR_CANDIDATES] (the merge, whose host does not know their number).
+template <class SOURCE>
+__device__ __forceinline__ void has_data_body(SOURCE &source, const VolumeP &dst, long long first, long long end, bool countCandidates,
+                                              int32_t *__restrict__ info, uint32_t *__restrict__ bucketOut, int32_t *__restrict__ res) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (long long i = first + (long long)blockIdx.x * 4 + wave; i < end; i += (long long)gridDim.x * 4) {
+    int b[3];
+    if (!source.candidate(i, b)) {
+      if (lane == 0) { info[i] = -2; bucketOut[i] = kMergeNoBucket; }
+      continue;
+    }
+    source.prepare(b);
+    bool any = false;
+#pragma unroll 1
+    for (int x = 0; x < 8 && !any; ++x) {  // ends as soon as a lane of the wave has seen data
+      const MergeSample s = source.sample(b[0] * 8 + x, b[1] * 8 + (lane & 7), b[2] * 8 + (lane >> 3));
+      any = __any(s.valid) != 0;
+    }
+    if (lane == 0) {
+      int entry = -2;
+      uint32_t bucket = kMergeNoBucket;
+      if (any) {
+        entry = chain_find(dst, b[0], b[1], b[2]).entry;
+        if (entry < 0) { bucket = hash_index(b[0], b[1], b[2], dst.mask); atomicAdd(&res[MR_NEEDED], 1); }
+        atomicAdd(&res[MR_WITH_DATA], 1);
+      }
+      if (countCandidates) atomicAdd(&res[MR_CANDIDATES], 1);
+      info[i] = entry;
+      bucketOut[i] = bucket;
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void k_merge_has_data(MergeP m, SceneP src, SceneP dst, const unsigned long long *__restrict__ cand,
                                                         const int32_t *__restrict__ nCandPtr, int first, int count,
                                                         int32_t *__restrict__ info, uint32_t *__restrict__ bucketOut,
                                                         int32_t *__restrict__ res) {
   __shared__ int boxPtrAll[4][64];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int *boxPtr = boxPtrAll[wave];
+  MergeVolumeSource source{m, VolumeP{src.table, src.vba, m.srcBuckets, m.srcMask}, cand,
+                           boxPtrAll[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)], (int)(threadIdx.x & 63)};
   const int nCand = *nCandPtr;
-  const int end = first + count < nCand ? first + count : nCand;
-  for (int i = first + blockIdx.x * 4 + wave; i < end; i += gridDim.x * 4) {
-    const unsigned long long key = cand[i];
-    if (key == kMergeNoKey) {  // the one sentinel the de-duplication leaves
-      if (lane == 0) { info[i] = -2; bucketOut[i] = kMergeNoBucket; }
-      continue;
-    }
-    int bx, by, bz;
-    merge_unkey(key, bx, by, bz);
-    __builtin_amdgcn_wave_barrier();
-    const MergeBox box = merge_resolve_box(m, src, bx, by, bz, boxPtr, lane);
-    MergeVoxCache cache; cache.bx = cache.by = cache.bz = 0x7fffffff; cache.ptr = -1;
-    bool any = false;
-#pragma unroll 1
-    for (int x = 0; x < 8 && !any; ++x) {  // ends as soon as a lane of the wave has seen data
-      const MergeSample s = merge_sample(m, src, box, boxPtr, cache, bx * 8 + x, by * 8 + (lane & 7), bz * 8 + (lane >> 3));
-      any = __any(s.valid) != 0;
-    }
-    if (lane == 0) {
-      int ptr, entry = -2;
-      uint32_t bucket = kMergeNoBucket;
-      if (any) {
-        entry = merge_find_entry(dst.table, m.dstBuckets, m.dstMask, bx, by, bz, ptr);
-        if (entry < 0) { bucket = hash_index(bx, by, bz, m.dstMask); atomicAdd(&res[MR_NEEDED], 1); }
-        atomicAdd(&res[MR_WITH_DATA], 1);
-      }
-      atomicAdd(&res[MR_CANDIDATES], 1);
-      info[i] = entry;
-      bucketOut[i] = bucket;
-    }
-  }
+  has_data_body(source, VolumeP{dst.table, dst.vba, m.dstBuckets, m.dstMask}, first, first + count < nCand ? first + count : nCand, true,
+                info, bucketOut, res);
 }
 
 // ------------------------------------------------------------------ the ordered insert
@@ -357,28 +272,20 @@ __global__ void k_merge_finish(SceneP dst, int32_t *__restrict__ res) {
 
 // ------------------------------------------------------------------ the write pass
 
-// One wave per candidate with data that has (or just got) a block in dst; lane = the 8 voxels of one x-row, read and written as
-// whole vectors of the sdf, weight and colour planes.
-__global__ __launch_bounds__(256) void k_merge_pull(MergeP m, SceneP src, SceneP dst, const unsigned long long *__restrict__ cand,
-                                                    const int32_t *__restrict__ nCandPtr, int first, int count,
-                                                    const int32_t *__restrict__ info, unsigned long long *__restrict__ voxelsUpdated) {
-  __shared__ int boxPtrAll[4][64];
+// One wave per candidate in [first, end) with data that has (or just got) a block in dst; lane = the 8 voxels of one x-row, read
+// and written as whole vectors of the sdf, weight and colour planes.  combine: the sample is merged into the voxel, else it
+// replaces it; colour: the samples carry colour.
+template <class SOURCE>
+__device__ __forceinline__ void pull_body(SOURCE &source, const VolumeP &dst, long long first, long long end, bool combine, bool colour,
+                                          int maxW, const int32_t *__restrict__ info, unsigned long long *__restrict__ voxelsUpdated) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int *boxPtr = boxPtrAll[wave];
-  const int nCand = *nCandPtr;
-  const int end = first + count < nCand ? first + count : nCand;
-  for (int i = first + blockIdx.x * 4 + wave; i < end; i += gridDim.x * 4) {
-    if (info[i] < -1) continue;
-    int bx, by, bz;
-    merge_unkey(cand[i], bx, by, bz);
-    int dptr;
-    merge_find_entry(dst.table, m.dstBuckets, m.dstMask, bx, by, bz, dptr);
-    dptr = __builtin_amdgcn_readfirstlane(dptr);
+  for (long long i = first + (long long)blockIdx.x * 4 + wave; i < end; i += (long long)gridDim.x * 4) {
+    int b[3];
+    if (info[i] < -1 || !source.candidate(i, b)) continue;
+    const int dptr = __builtin_amdgcn_readfirstlane(chain_find(dst, b[0], b[1], b[2]).ptr);
     if (dptr < 0) continue;  // dropped: dst had no block left for it
-    __builtin_amdgcn_wave_barrier();
-    const MergeBox box = merge_resolve_box(m, src, bx, by, bz, boxPtr, lane);
-    MergeVoxCache cache; cache.bx = cache.by = cache.bz = 0x7fffffff; cache.ptr = -1;
+    source.prepare(b);
     uint8_t *blk = dst.vba + (size_t)dptr * kBlockBytes;
     union { uint4 v; short s[8]; } sdf;
     union { uint2 v; uint8_t b[8]; } wd;
@@ -391,13 +298,20 @@ __global__ __launch_bounds__(256) void k_merge_pull(MergeP m, SceneP src, SceneP
     bool clrChanged = false;
 #pragma unroll
     for (int x = 0; x < 8; ++x) {
-      const MergeSample s = merge_sample(m, src, box, boxPtr, cache, bx * 8 + x, by * 8 + (lane & 7), bz * 8 + (lane >> 3));
+      const MergeSample s = source.sample(b[0] * 8 + x, b[1] * 8 + (lane & 7), b[2] * 8 + (lane >> 3));
       if (!s.valid) continue;
-      short sv = sdf.s[x];
-      int w = wd.b[x];
-      merge_combine_depth(s.g, s.w, m.maxW, sv, w);
-      sdf.s[x] = sv; wd.b[x] = (uint8_t)w;
-      if (m.mergeColour && s.clr.w > 0) { clr.c[x] = merge_combine_colour(s.clr, clr.c[x], m.maxW); clrChanged = true; }
+      if (combine) {
+        // combine_voxel_* with the sample in the role of the stored copy.  Their early returns (weight 0) are never taken here:
+        // a sample's weight is at least minW >= 1, and its colour is combined only when its w_color > 0
+        short sv = sdf.s[x];
+        int w = wd.b[x];
+        combine_voxel_depth(s.g, s.w, maxW, sv, w);
+        sdf.s[x] = sv; wd.b[x] = (uint8_t)w;
+        if (colour && s.clr.w > 0) { clr.c[x] = combine_voxel_colour(s.clr, clr.c[x], maxW); clrChanged = true; }
+      } else {
+        sdf.s[x] = s.g; wd.b[x] = (uint8_t)(s.w < maxW ? s.w : maxW);
+        if (colour) { clr.c[x] = s.clr; clrChanged = true; }
+      }
       updated++;
     }
     if (updated) {
@@ -413,6 +327,17 @@ __global__ __launch_bounds__(256) void k_merge_pull(MergeP m, SceneP src, SceneP
     for (int d = 1; d < 64; d <<= 1) total += __shfl_xor(total, d);
     if (lane == 0 && total) atomicAdd(voxelsUpdated, (unsigned long long)total);
   }
+}
+
+__global__ __launch_bounds__(256) void k_merge_pull(MergeP m, SceneP src, SceneP dst, const unsigned long long *__restrict__ cand,
+                                                    const int32_t *__restrict__ nCandPtr, int first, int count,
+                                                    const int32_t *__restrict__ info, unsigned long long *__restrict__ voxelsUpdated) {
+  __shared__ int boxPtrAll[4][64];
+  MergeVolumeSource source{m, VolumeP{src.table, src.vba, m.srcBuckets, m.srcMask}, cand,
+                           boxPtrAll[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)], (int)(threadIdx.x & 63)};
+  const int nCand = *nCandPtr;
+  pull_body(source, VolumeP{dst.table, dst.vba, m.dstBuckets, m.dstMask}, first, first + count < nCand ? first + count : nCand, true,
+            m.mergeColour != 0, m.maxW, info, voxelsUpdated);
 }
 
 }  // namespace dsr

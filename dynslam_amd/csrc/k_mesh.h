@@ -16,7 +16,7 @@
 //           second 9x9x9 lattice, of the (r, g, b, w_color) words of the same 8 blocks, beside the sdf one; next to every triangle
 //           the colours of its three vertices (vertex_colour), at the same slot.  Every other instantiation compiles without that part.
 #pragma once
-#include "dsr_device.h"
+#include "dsr_sample.h"
 #include "../../include/dsr_mesh.h"
 
 #define MC_TABLE_ATTR __constant__ static const
@@ -113,15 +113,9 @@ __global__ __launch_bounds__(64 * kMeshWaves) void k_mesh_blocks(SceneP s, MeshP
     // ---- the 8 blocks the lattice touches: lane k looks up block pos + (k&1, k>>1&1, k>>2)
     if (lane < 8) {
       const int bx = he.pos[0] + (lane & 1), by = he.pos[1] + ((lane >> 1) & 1), bz = he.pos[2] + (lane >> 2);
-      int ptr = -1;
-      uint32_t h = hash_index(bx, by, bz, mp.hashMask);
-      while (true) {  // ITMRepresentationAccess.h findVoxel
-        const dsr_hash_entry q = load_entry(s.table, h);
-        if (q.pos[0] == bx && q.pos[1] == by && q.pos[2] == bz && src.owns(s, h, q.ptr)) { ptr = src.locate(h, q.ptr); break; }
-        if (q.offset < 1) break;
-        h = (uint32_t)(mp.noBuckets + q.offset - 1);
-      }
-      nbr[lane] = ptr;
+      const ChainHit hit = chain_walk(s.table, mp.noBuckets, mp.hashMask, bx, by, bz,
+                                      [&](uint32_t h, int ptr) { return src.owns(s, h, ptr); });
+      nbr[lane] = hit.entry >= 0 ? src.locate((uint32_t)hit.entry, hit.ptr) : -1;
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();

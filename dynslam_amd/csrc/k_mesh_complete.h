@@ -73,6 +73,20 @@ struct MeshPooledColour : MeshPooled {
   }
 };
 
+// the owning entry of block (bx, by, bz), if its plane has to come from the store and has none yet, gets the pool's next plane
+__device__ __forceinline__ void mesh_mark_block(const SceneP &s, const MeshP &mp, int bx, int by, int bz, int32_t *__restrict__ planeOf,
+                                                int32_t *__restrict__ poolIds, int poolCap, int32_t *__restrict__ ctrs) {
+  const ChainHit hit = chain_walk(s.table, mp.noBuckets, mp.hashMask, bx, by, bz,
+                                  [&](uint32_t h, int) { return entry_listed<true>(s, (int)h); });
+  if (hit.entry < 0) return;
+  const uint32_t h = (uint32_t)hit.entry;
+  if (plane_from_store(s, h, hit.ptr) && atomicCAS(&planeOf[h], -1, -2) == -1) {
+    const int slot = atomicAdd(&ctrs[0], 1);
+    if (slot < poolCap) { poolIds[slot] = (int)h; planeOf[h] = slot; }
+    else { planeOf[h] = -1; ctrs[1] = 1; }
+  }
+}
+
 // ctrs[0]: planes handed out, ctrs[1]: 1 = the pool was too small (cannot happen with 8 planes per listed entry; the host checks)
 __global__ __launch_bounds__(256) void k_mesh_mark(SceneP s, MeshP mp, const int32_t *__restrict__ blockList,
                                                    const int32_t *__restrict__ nPtr, int firstItem, int endItem,
@@ -84,21 +98,7 @@ __global__ __launch_bounds__(256) void k_mesh_mark(SceneP s, MeshP mp, const int
   if (item >= n) return;
   const int k = (int)(tid & 7);
   const dsr_hash_entry he = load_entry(s.table, (uint32_t)blockList[item]);
-  const int bx = he.pos[0] + (k & 1), by = he.pos[1] + ((k >> 1) & 1), bz = he.pos[2] + (k >> 2);
-  uint32_t h = hash_index(bx, by, bz, mp.hashMask);
-  while (true) {
-    const dsr_hash_entry q = load_entry(s.table, h);
-    if (q.pos[0] == bx && q.pos[1] == by && q.pos[2] == bz && entry_listed<true>(s, (int)h)) {
-      if (plane_from_store(s, h, q.ptr) && atomicCAS(&planeOf[h], -1, -2) == -1) {
-        const int slot = atomicAdd(&ctrs[0], 1);
-        if (slot < poolCap) { poolIds[slot] = (int)h; planeOf[h] = slot; }
-        else { planeOf[h] = -1; ctrs[1] = 1; }
-      }
-      break;
-    }
-    if (q.offset < 1) break;
-    h = (uint32_t)(mp.noBuckets + q.offset - 1);
-  }
+  mesh_mark_block(s, mp, he.pos[0] + (k & 1), he.pos[1] + ((k >> 1) & 1), he.pos[2] + (k >> 2), planeOf, poolIds, poolCap, ctrs);
 }
 
 // pool plane i <- the sdf plane entry poolIds[i] has after its next swap-in.  Lane l: voxels 8 l .. 8 l + 7 (16 B of sdf, 8 B of

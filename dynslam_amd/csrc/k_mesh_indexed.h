@@ -43,16 +43,11 @@ __device__ __forceinline__ void stage_lattice27(const SceneP &s, const MeshP &mp
                                                 int *nbr, int *nbrEntry, int *lat) {
   if (lane < 27) {
     const int bx = he.pos[0] + lane % 3 - 1, by = he.pos[1] + (lane / 3) % 3 - 1, bz = he.pos[2] + lane / 9 - 1;
-    int code = -1, entry = -1;
-    uint32_t h = hash_index(bx, by, bz, mp.hashMask);
-    while (true) {  // ITMRepresentationAccess.h findVoxel
-      const dsr_hash_entry q = load_entry(s.table, h);
-      if (q.pos[0] == bx && q.pos[1] == by && q.pos[2] == bz && src.owns(s, h, q.ptr)) { code = src.locate(h, q.ptr); entry = (int)h; break; }
-      if (q.offset < 1) break;
-      h = (uint32_t)(mp.noBuckets + q.offset - 1);
-    }
+    const ChainHit hit = chain_walk(s.table, mp.noBuckets, mp.hashMask, bx, by, bz,
+                                    [&](uint32_t h, int ptr) { return src.owns(s, h, ptr); });
+    const int code = hit.entry >= 0 ? src.locate((uint32_t)hit.entry, hit.ptr) : -1;
     nbr[lane] = code;
-    nbrEntry[lane] = src.has(code) ? entry : -1;
+    nbrEntry[lane] = src.has(code) ? hit.entry : -1;
   }
   mesh_wave_sync();
   for (int c = lane; c < kLat11; c += 64) {
@@ -295,21 +290,7 @@ __global__ __launch_bounds__(256) void k_mesh_mark27(SceneP s, MeshP mp, const i
   if (item >= n) return;
   const int k = (int)(tid % 27);
   const dsr_hash_entry he = load_entry(s.table, (uint32_t)blockList[item]);
-  const int bx = he.pos[0] + k % 3 - 1, by = he.pos[1] + (k / 3) % 3 - 1, bz = he.pos[2] + k / 9 - 1;
-  uint32_t h = hash_index(bx, by, bz, mp.hashMask);
-  while (true) {
-    const dsr_hash_entry q = load_entry(s.table, h);
-    if (q.pos[0] == bx && q.pos[1] == by && q.pos[2] == bz && entry_listed<true>(s, (int)h)) {
-      if (plane_from_store(s, h, q.ptr) && atomicCAS(&planeOf[h], -1, -2) == -1) {
-        const int slot = atomicAdd(&ctrs[0], 1);
-        if (slot < poolCap) { poolIds[slot] = (int)h; planeOf[h] = slot; }
-        else { planeOf[h] = -1; ctrs[1] = 1; }
-      }
-      break;
-    }
-    if (q.offset < 1) break;
-    h = (uint32_t)(mp.noBuckets + q.offset - 1);
-  }
+  mesh_mark_block(s, mp, he.pos[0] + k % 3 - 1, he.pos[1] + (k / 3) % 3 - 1, he.pos[2] + k / 9 - 1, planeOf, poolIds, poolCap, ctrs);
 }
 
 }  // namespace dsr

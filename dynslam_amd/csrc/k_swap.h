@@ -114,34 +114,7 @@ __global__ __launch_bounds__(256) void k_swapin_fetch(SceneP s, const int32_t *_
   }
 }
 
-// ITMSwappingEngine.h combineVoxelDepthInformation on one voxel: (sdf, w) of the local block <- its merge with the stored copy's
-// (oldSdf, oldW).  Shared with the complete mesher (k_mesh_complete.h), which needs the sdf the next swap-in WOULD leave.
-__device__ __forceinline__ void combine_voxel_depth(short oldSdf, int oldW, int maxW, short &sdf, int &w) {
-  if (oldW == 0) return;
-  float newF = sdf_to_float((float)sdf);
-  const float oldF = sdf_to_float((float)oldSdf);
-  newF = (float)oldW * oldF + (float)w * newF;
-  w = oldW + w;
-  newF /= (float)w;
-  w = w < maxW ? w : maxW;
-  sdf = sdf_from_float(newF);
-}
-// ... combineVoxelColorInformation, on the (r, g, b, w_color) word
-__device__ __forceinline__ uchar4 combine_voxel_colour(uchar4 sc, uchar4 dc, int maxW) {
-  int newW = dc.w;
-  const int oldW = sc.w;
-  if (oldW == 0) return dc;
-  float nx = (float)dc.x / 255.0f, ny = (float)dc.y / 255.0f, nz = (float)dc.z / 255.0f;
-  const float ox = (float)sc.x / 255.0f, oy = (float)sc.y / 255.0f, oz = (float)sc.z / 255.0f;
-  nx = ox * (float)oldW + nx * (float)newW;
-  ny = oy * (float)oldW + ny * (float)newW;
-  nz = oz * (float)oldW + nz * (float)newW;
-  newW = oldW + newW;
-  nx /= (float)newW; ny /= (float)newW; nz /= (float)newW;
-  newW = newW < maxW ? newW : maxW;
-  return make_uchar4((uint8_t)f2i(nx * 255.0f), (uint8_t)f2i(ny * 255.0f), (uint8_t)f2i(nz * 255.0f), (uint8_t)newW);
-}
-// src (the stored copy) merged into dst, both plane-wise blocks; this lane's 8 voxels
+// src (the stored copy) merged into dst, both plane-wise blocks (dsr_device.h combine_voxel_*); this lane's 8 voxels
 __device__ __forceinline__ void combine_block_lane(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, int lane, int maxW) {
 #pragma unroll 1
   for (int x = 0; x < 8; ++x) {

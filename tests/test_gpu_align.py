@@ -253,3 +253,21 @@ def test_shim_align_from(through_driver, tmp_path):
     assert raw[20:84] == mu.colmajor(res["src_to_dst"]).tobytes(), "the refined transform"
     printed = np.array([[float(x) for x in line.split()] for line in out.stdout.strip().splitlines()], F)
     assert printed.tobytes() == res["src_to_dst"].tobytes(), "the printed transform"
+
+
+# the lookup behind the box: no src block's dst blocks fit the wave's 4 x 4 x 4 box
+def test_wide_src_voxels_take_the_lookup_behind_the_box(vols):
+    """A src of 0.175 m voxels against B's 0.035 m: the 8-voxel edge of a src block spans 7 * 5 = 35 dst voxels, and a cube's extent
+    along any axis is at least its edge under any rotation; with the box's margins (-1 / +2) that is a range of at least 38 voxels,
+    which meets more than 4 blocks of 8: the box is off for every src block, and every dst block is found through the lane's cache
+    and the chain walk.  (The other alignment tests have at most 1.43 dst voxels per src voxel: their box is always on.)"""
+    wide = dict(au.A, voxel_size=0.175, mu=0.7)   # mu in proportion to the voxel size
+    src = _engine(wide, (0, 1, 2))
+    try:
+        params = dict(stride=(1,), iterations=(2,))
+        got = vols["e"]["B"].align_from(src, au.INIT, **params)
+        want = au.run_ref(vols["st"]["B"], au.B, au.state(src), wide, au.INIT, **params)
+        assert want["log_count"] == 2 and want["log"][0]["valid_points"] > 0
+        au.assert_result_equal(got, want, "0.175 m src -> B")
+    finally:
+        src.close()

@@ -433,3 +433,22 @@ def test_torch_tensors_out_and_in(fine):
     mu.assert_state_equal(states[0], states[1], "from_dense of tensors and of their numpy copies")
     with pytest.raises(DsrError):
         e.from_dense(dev["sdf"].cpu(), pitch=PITCH)   # a tensor that is not on the engine's GPU
+
+
+# the lookup behind the box: no tile's engine blocks fit the wave's 4 x 4 x 4 box
+WIDE_SHAPE, WIDE_PITCH = (9, 6, 5), 0.175   # 5 voxels of the FINE volume per grid point; the grid covers the volume's bulk
+
+
+@pytest.mark.parametrize("sampling", ["trilinear", "nearest"])
+def test_wide_pitch_export_takes_the_lookup_behind_the_box(fine, sampling):
+    """The box is computed for the whole 16 x 4 x 4 tile, also at the grid's edge: 75 x 15 x 15 voxels here.  Under any rotation one
+    volume axis sees at least 75 / sqrt(3) = 43 voxels of the long edge; with the box's margins (-1 / +2) that is a range of at
+    least 46 voxels, which meets more than 4 blocks of 8: the box is off for every tile, and every block is found through the
+    lane's cache and the chain walk.  (The other export tests have at most 1.15 voxels per grid point: their box is always on.)"""
+    e, st = fine["e"], fine["state"]
+    T = du.place_rigid(st, mu.FINE, WIDE_SHAPE, WIDE_PITCH)
+    want, n_want = du.ref_export(st, mu.FINE, du.grid_spec(WIDE_SHAPE, WIDE_PITCH, T, sampling=sampling))
+    assert n_want > 0
+    host = e.to_dense(WIDE_SHAPE[::-1], WIDE_PITCH, T, sampling=sampling)
+    assert host["points_with_data"] == n_want
+    _assert_planes_equal(host, want, f"pitch {WIDE_PITCH}, {sampling}")

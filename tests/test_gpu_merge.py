@@ -251,3 +251,25 @@ def test_shim_merge_from(merged, tmp_path):
     nt = after["table"].nbytes
     assert raw[24:24 + nt] == after["table"].tobytes(), "hash table"
     assert raw[24 + nt:] == np.ascontiguousarray(after["voxels"]).tobytes(), "voxel blocks"
+
+
+# 10. the lookup behind the box: no dst block's src blocks fit the wave's 4 x 4 x 4 box
+WIDE = dict(mu.COARSE, voxel_size=0.175, mu=0.7)   # 5 src voxels per dst voxel; mu in proportion, so that rescaled samples stay above -1
+
+
+def test_wide_dst_voxels_take_the_lookup_behind_the_box(hip_api):
+    """The 8-voxel edge of a dst block spans 7 * 5 = 35 src voxels, and a cube's extent along any axis is at least its edge under
+    any rotation; with the box's margins (-1 / +2 voxels) that is a range of at least 38 voxels, which meets more than 4 blocks of
+    8: the box is off for every dst block, and every src block is found through the lane's cache and the chain walk.  (The other
+    merge tests have at most 1.43 src voxels per dst voxel: their box is always on.)"""
+    src, dst = _engine(mu.FINE, mu.SRC_FRAMES), _engine(WIDE, mu.DST_FRAMES)
+    try:
+        b_dst, b_src = mu.state(dst), mu.state(src)
+        res = dst.merge_from(src, mu.RIGID)
+        status, want, want_res = mu.run_ref(b_dst, WIDE, b_src, mu.FINE, mu.RIGID)
+        assert status == 0 and want_res["voxels_updated"] > 0 and want_res["blocks_allocated"] > 0
+        assert res == want_res, (res, want_res)
+        mu.assert_state_equal(mu.state(dst), want, "fine into a 0.175 m volume")
+        check_structure(dst, WIDE["sdf_local_block_num"], WIDE["hash_bucket_num"])
+    finally:
+        src.close(); dst.close()
