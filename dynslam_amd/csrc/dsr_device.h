@@ -199,6 +199,38 @@ __device__ __forceinline__ uchar4 combine_voxel_colour(uchar4 sc, uchar4 dc, int
   return make_uchar4((uint8_t)f2i(nx * 255.0f), (uint8_t)f2i(ny * 255.0f), (uint8_t)f2i(nz * 255.0f), (uint8_t)newW);
 }
 
+// the block of host-store slot `slot` (k_swap.h: pinned slabs the GPU addresses directly)
+__device__ __forceinline__ uint8_t *host_block(const SceneP &s, int slot) {
+  return s.hostSlabs[slot / s.slabBlocks] + (size_t)(slot % s.slabBlocks) * kBlockBytes;
+}
+
+// src (the stored copy) merged into dst, both plane-wise blocks (combine_voxel_* above); this lane's 8 voxels
+__device__ __forceinline__ void combine_block_lane(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, int lane, int maxW) {
+#pragma unroll 1
+  for (int x = 0; x < 8; ++x) {
+    const int v = lane * 8 + x;
+    const int oldW = src[kOffWDepth + v];
+    if (oldW != 0) {  // depth
+      short sdf = *reinterpret_cast<const short *>(dst + kOffSdf + v * 2);
+      int w = dst[kOffWDepth + v];
+      combine_voxel_depth(*reinterpret_cast<const short *>(src + kOffSdf + v * 2), oldW, maxW, sdf, w);
+      dst[kOffWDepth + v] = (uint8_t)w;
+      *reinterpret_cast<short *>(dst + kOffSdf + v * 2) = sdf;
+    }
+    const uchar4 sc = *reinterpret_cast<const uchar4 *>(src + kOffClr + v * 4);  // (r, g, b, w_color)
+    if (sc.w != 0)
+      *reinterpret_cast<uchar4 *>(dst + kOffClr + v * 4) =
+          combine_voxel_colour(sc, *reinterpret_cast<const uchar4 *>(dst + kOffClr + v * 4), maxW);
+  }
+}
+
+// Is entry t on the ordered list of entries (k_decay.h k_allocated_* / k_owning_*)?  Every entry with ptr >= 0; STORED
+// (k_mesh_complete.h): every entry that owns voxel DATA — resident, or swapped out with a copy in the host store
+template <bool STORED>
+__device__ __forceinline__ bool entry_listed(const SceneP &s, int t) {
+  return s.table[t].ptr >= 0 || (STORED && s.swapStored && s.swapStored[t] != 0);
+}
+
 // The per-pixel / per-block functions of the range-image, visibility, raycast and shading kernels are templates over an Ops
 // policy — how to convert float -> int, round down / up, divide by a tame divisor, ask "any ray of the wave" —: the device's
 // instructions here, a one-ray host stand-in in tests/hostsim, under which tests/test_device_functions_host.py runs those very functions

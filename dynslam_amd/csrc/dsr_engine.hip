@@ -18,15 +18,11 @@ using namespace dsr_internal;
 #include "k_integrate.h"
 #include "k_raycast.h"
 #include "k_swap.h"
-#include "k_mesh.h"
-#include "k_mesh_complete.h"
-#include "k_mesh_indexed.h"
 #include "k_small.h"
 #include "k_batch.h"
 #include "k_batch_gc.h"
 #include "../../include/dsr_track.h"
 #include "../../include/dsr_gc.h"
-#include "../../include/dsr_mesh.h"
 
 // the volume batch's deferred work (paired render; defined with dsr_batch below, inside its extern "C" block)
 extern "C" {
@@ -502,14 +498,21 @@ int dsr_internal::engine_flush_deferred(dsr_engine *e) {
 void dsr_internal::engine_prof_resolve(dsr_engine *e) { prof_resolve(e); }
 // ---- for dsr_snapshot.hip (include/dsr_snapshot.h): the engine's own steps a snapshot is built from
 int dsr_internal::engine_reset(dsr_engine *e) { return reset_scene(e); }
-int dsr_internal::engine_list_allocated(dsr_engine *e) {
-  // the ascending list of the allocated entries, as Decay(forceAllVoxels) and meshing build it
-  LAUNCH(e, "snapshot_candidates", k_allocated_count, dim3(e->numTilesE), dim3(kTileThreads), e->scene, e->E, e->tileSums);
-  LAUNCH(e, "scan_tiles", k_scan_tile_sums, dim3(1), dim3(1024), e->tileSums, e->numTilesE, e->scene, (int)SCAN_NCAND, e->noBlocks);
-  LAUNCH(e, "snapshot_candidates", k_allocated_write, dim3(e->numTilesE), dim3(kTileThreads), e->scene, e->E,
-         (const int2 *)e->tileSums, e->decayCand, e->noBlocks);
-  HIP_TRY(hipGetLastError());
-  return DSR_OK;
+void dsr_internal::engine_list_entries(dsr_engine *e, const char *label, bool owning, const SceneP &sc, int2 *tileSums, int32_t *out,
+                                       int capacity, int lengthCtr) {
+  const int scanMode = lengthCtr == CTR_NO_ALLOCATED ? SCAN_ALLOCATED : SCAN_NCAND;
+  if (owning) LAUNCH(e, label, k_owning_count, dim3(e->numTilesE), dim3(kTileThreads), sc, e->E, tileSums);
+  else LAUNCH(e, label, k_allocated_count, dim3(e->numTilesE), dim3(kTileThreads), sc, e->E, tileSums);
+  LAUNCH(e, "scan_tiles", k_scan_tile_sums, dim3(1), dim3(1024), tileSums, e->numTilesE, sc, scanMode, capacity);
+  if (owning) LAUNCH(e, label, k_owning_write, dim3(e->numTilesE), dim3(kTileThreads), sc, e->E, (const int2 *)tileSums, out, capacity);
+  else LAUNCH(e, label, k_allocated_write, dim3(e->numTilesE), dim3(kTileThreads), sc, e->E, (const int2 *)tileSums, out, capacity);
+}
+void dsr_internal::engine_scan_counts(dsr_engine *e, const SceneP &sc, const uint32_t *counts, const int32_t *nPtr, int n, int2 *tileSums,
+                                      uint32_t *offsets) {
+  const int tiles = div_up(n, kTile);
+  LAUNCH(e, "mesh_scan", k_u32_tile_sums, dim3(tiles), dim3(kTileThreads), counts, nPtr, tileSums);
+  LAUNCH(e, "scan_tiles", k_scan_tile_sums, dim3(1), dim3(1024), tileSums, tiles, sc, (int)SCAN_MESH, 0);
+  LAUNCH(e, "mesh_scan", k_u32_tile_offsets, dim3(tiles), dim3(kTileThreads), counts, nPtr, (const int2 *)tileSums, offsets);
 }
 int dsr_internal::engine_ensure_fifo(dsr_engine *e, int slots) { return ensure_fifo(e, slots); }
 int dsr_internal::engine_add_host_slab(dsr_engine *e) { return add_host_slab(e); }
@@ -945,11 +948,7 @@ int dsr_decay(dsr_engine *e, int max_weight, int min_age, int force_all_voxels) 
   const int32_t *cand = nullptr;
   const int32_t *nCandPtr = nullptr;
   if (force_all_voxels) {
-    LAUNCH(e, "decay_candidates", k_allocated_count, dim3(e->numTilesE), dim3(kTileThreads), e->scene, e->E, e->tileSums);
-    LAUNCH(e, "scan_tiles", k_scan_tile_sums, dim3(1), dim3(1024), e->tileSums, e->numTilesE, e->scene, (int)SCAN_NCAND,
-           e->noBlocks);
-    LAUNCH(e, "decay_candidates", k_allocated_write, dim3(e->numTilesE), dim3(kTileThreads), e->scene, e->E,
-           (const int2 *)e->tileSums, e->decayCand, e->noBlocks);
+    engine_list_entries(e, "decay_candidates", false, e->scene, e->tileSums, e->decayCand, e->noBlocks);
     cand = e->decayCand;
     nCandPtr = e->scene.ctr + CTR_DECAY_NCAND;
   } else {
@@ -1113,11 +1112,7 @@ static int render_common(dsr_engine *e, int type, const float pose_m[16], const 
       // FindVisibleBlocks: the allocated entries (ascending list, rebuilt when the scene has changed)
       // are tested densely against the free camera's frustum, the visible ones compacted in order
       if (e->allocListVersion != e->sceneVersion) {
-        LAUNCH(e, "allocated_list", k_allocated_count, dim3(e->numTilesE), dim3(kTileThreads), e->scene, e->E, e->tileSums);
-        LAUNCH(e, "scan_tiles", k_scan_tile_sums, dim3(1), dim3(1024), e->tileSums, e->numTilesE, e->scene,
-               (int)SCAN_ALLOCATED, e->noBlocks);
-        LAUNCH(e, "allocated_list", k_allocated_write, dim3(e->numTilesE), dim3(kTileThreads), e->scene, e->E,
-               (const int2 *)e->tileSums, e->allocList, e->noBlocks);
+        engine_list_entries(e, "allocated_list", false, e->scene, e->tileSums, e->allocList, e->noBlocks, CTR_NO_ALLOCATED);
         e->allocListVersion = e->sceneVersion;
       }
       const int32_t *nAlloc = e->scene.ctr + CTR_NO_ALLOCATED;
@@ -1669,579 +1664,6 @@ int dsr_dump_stored_block(dsr_engine *e, int entry, dsr_voxel *out, int *present
       out[v] = o;
     }
   }
-  return DSR_OK;
-}
-
-// ---- meshing
-
-extern "C++" {  // (templates: this part of the file sits inside the extern "C" block of the ABI)
-namespace {
-int mesh_release(dsr_engine *e) {
-  if (e->meshTris || e->meshClr) HIP_TRY(hipStreamSynchronize(e->stream));
-  if (e->meshTris) { (void)hipFree(e->meshTris); e->meshTris = nullptr; }
-  if (e->meshClr) { (void)hipFree(e->meshClr); e->meshClr = nullptr; }
-  e->meshCount = 0;
-  e->meshColoured = false;
-  return DSR_OK;
-}
-
-// device scratch of one meshing call, freed when the call returns (every kernel that used it has run by then: the calls wait)
-struct MeshScratch {
-  std::vector<void *> bufs;
-  template <class T>
-  int get(T **p, size_t n) {
-    if (hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess)
-      return fail(DSR_E_NOMEM, "mesh scratch allocation failed");
-    bufs.push_back(*p);
-    return DSR_OK;
-  }
-  ~MeshScratch() { for (void *b : bufs) (void)hipFree(b); }
-};
-
-// Marching cubes over the ordered list of n entries (its length on the device: *nPtr), in chunks of `chunk` entries: count per
-// block, scan, write.  prep(first, end, src) fills the kernel's policy for a chunk and queues what readies its data — nothing for
-// the resident mesher; a mesh of ONE chunk prepares once, its data still stands in the write pass.  sc: the scene, with the
-// counters the scan may write (SCAN_MESH).  The mesh lands in e->meshTris / meshCount; COLOUR: the write pass is the coloured one
-// (MeshColoured<SRC>; SRC has clr_plane) and the vertex colours land in e->meshClr.
-template <class SRC, bool COLOUR = false, class PREP>
-int mesh_from_list(dsr_engine *e, const SceneP &sc, const int32_t *list, const int32_t *nPtr, int n, int2 *tileSums,
-                   unsigned long long cap, int chunk, PREP prep) {
-  MeshScratch scratch;
-  uint32_t *blockCount = nullptr, *blockOffset = nullptr;
-  int st;
-  if ((st = scratch.get(&blockCount, (size_t)n)) || (st = scratch.get(&blockOffset, (size_t)n))) return st;
-  MeshP mp; mp.voxelSize = e->s.voxel_size; mp.hashMask = (uint32_t)(e->noBuckets - 1); mp.noBuckets = e->noBuckets;
-  const int tiles = div_up(n, kTile);
-  const bool oneChunk = n <= chunk;
-  SRC src{};
-  for (int first = 0; first < n; first += chunk) {
-    const int end = (int)std::min<long long>((long long)first + chunk, n);
-    if ((st = prep(first, end, src))) return st;
-    LAUNCH(e, "mesh_count", (k_mesh_blocks<false, SRC>), dim3(std::min(8192, div_up(end - first, kMeshWaves))), dim3(64 * kMeshWaves),
-           sc, mp, list, nPtr, blockCount, (const uint32_t *)nullptr, (dsr_triangle *)nullptr, 0ull, src);
-  }
-  LAUNCH(e, "mesh_scan", k_u32_tile_sums, dim3(tiles), dim3(kTileThreads), (const uint32_t *)blockCount, nPtr, tileSums);
-  LAUNCH(e, "scan_tiles", k_scan_tile_sums, dim3(1), dim3(1024), tileSums, tiles, sc, (int)SCAN_MESH, 0);
-  LAUNCH(e, "mesh_scan", k_u32_tile_offsets, dim3(tiles), dim3(kTileThreads), (const uint32_t *)blockCount, nPtr,
-         (const int2 *)tileSums, blockOffset);
-  int total = 0;
-  HIP_TRY(hipMemcpyAsync(&total, sc.ctr + CTR_MESH_TOTAL, 4, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  if (total < 0) return fail(DSR_E_ARG, "mesh has more than 2^31 triangles");
-  const unsigned long long keep = std::min((unsigned long long)total, cap);
-  if (keep == 0) return DSR_OK;
-  if (hipMalloc(reinterpret_cast<void **>(&e->meshTris), (size_t)keep * sizeof(dsr_triangle)) != hipSuccess) {
-    e->meshTris = nullptr;
-    return fail(DSR_E_NOMEM, "mesh triangle buffer allocation failed");
-  }
-  if (COLOUR && hipMalloc(reinterpret_cast<void **>(&e->meshClr), (size_t)keep * sizeof(dsr_triangle_colour)) != hipSuccess) {
-    (void)hipFree(e->meshTris); e->meshTris = nullptr; e->meshClr = nullptr;
-    return fail(DSR_E_NOMEM, "mesh colour buffer allocation failed");
-  }
-  for (int first = 0; first < n && st == DSR_OK; first += chunk) {
-    const int end = (int)std::min<long long>((long long)first + chunk, n);
-    if (!oneChunk && (st = prep(first, end, src))) break;
-    if constexpr (COLOUR) {
-      MeshColoured<SRC> csrc;
-      static_cast<SRC &>(csrc) = src;
-      csrc.colours = e->meshClr;
-      LAUNCH(e, "mesh_write_colour", (k_mesh_blocks<true, MeshColoured<SRC>>), dim3(std::min(8192, div_up(end - first, kMeshWaves))),
-             dim3(64 * kMeshWaves), sc, mp, list, nPtr, blockCount, (const uint32_t *)blockOffset, e->meshTris, keep, csrc);
-    }
-    else {
-      LAUNCH(e, "mesh_write", (k_mesh_blocks<true, SRC>), dim3(std::min(8192, div_up(end - first, kMeshWaves))), dim3(64 * kMeshWaves),
-             sc, mp, list, nPtr, blockCount, (const uint32_t *)blockOffset, e->meshTris, keep, src);
-    }
-  }
-  const hipError_t err = hipStreamSynchronize(e->stream);  // (also before the scratch goes)
-  if (st == DSR_OK && err != hipSuccess) st = fail(DSR_E_DEVICE, hipGetErrorString(err));
-  if (st == DSR_OK) e->meshCount = keep;
-  else {
-    (void)hipFree(e->meshTris); e->meshTris = nullptr;
-    if (e->meshClr) { (void)hipFree(e->meshClr); e->meshClr = nullptr; }
-  }
-  return st;
-}
-int no_prep(int, int, MeshResident &) { return DSR_OK; }
-long long host_store_slots(const dsr_engine *e) { return (long long)e->hostSlabs.size() * e->scene.slabBlocks; }
-template <bool COLOUR> int mesh_resident(dsr_engine *e, uint64_t *n_triangles);
-template <bool COLOUR> int mesh_complete(dsr_engine *e, uint64_t *n_triangles);
-}  // namespace
-}  // extern "C++"
-
-int dsr_mesh_free(dsr_engine *e) {
-  CHECK_E(e);
-  return mesh_release(e);
-}
-
-// ITMMeshingEngine::MeshScene (an offline dump: host synchronisation is fine here)
-int dsr_mesh_scene(dsr_engine *e, uint64_t *n_triangles) { return mesh_resident<false>(e, n_triangles); }
-
-extern "C++" {
-namespace {
-template <bool COLOUR>
-int mesh_resident(dsr_engine *e, uint64_t *n_triangles) {
-  CHECK_E(e);
-  int st = mesh_release(e);
-  if (st) return st;
-  // ascending list of the allocated entries (shared with Decay(forceAllVoxels))
-  LAUNCH(e, "mesh_candidates", k_allocated_count, dim3(e->numTilesE), dim3(kTileThreads), e->scene, e->E, e->tileSums);
-  LAUNCH(e, "scan_tiles", k_scan_tile_sums, dim3(1), dim3(1024), e->tileSums, e->numTilesE, e->scene, (int)SCAN_NCAND, e->noBlocks);
-  LAUNCH(e, "mesh_candidates", k_allocated_write, dim3(e->numTilesE), dim3(kTileThreads), e->scene, e->E,
-         (const int2 *)e->tileSums, e->decayCand, e->noBlocks);
-  const int32_t *nPtr = e->scene.ctr + CTR_DECAY_NCAND;
-  int n = 0;
-  HIP_TRY(hipMemcpyAsync(&n, nPtr, 4, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  if (n_triangles) *n_triangles = 0;
-  if (n <= 0) return DSR_OK;
-  // ITMMesh: noMaxTriangles = maxBlocks * 32; the append keeps the first noMaxTriangles - 1
-  const unsigned long long cap = (unsigned long long)e->noBlocks * 32ull - 1ull;
-  st = mesh_from_list<MeshResident, COLOUR>(e, e->scene, e->decayCand, nPtr, n, e->tileSums, cap, n, no_prep);
-  if (st == DSR_OK && n_triangles) *n_triangles = e->meshCount;
-  return st;
-}
-}  // namespace
-}  // extern "C++"
-
-// ---- the complete mesh of a swapping engine (include/dsr_mesh.h, k_mesh_complete.h; builder-defined)
-
-int32_t dsr_mesh_abi_version(void) { return DSR_MESH_ABI_VERSION; }
-
-int dsr_mesh_scene_complete(dsr_engine *e, uint64_t *n_triangles) { return mesh_complete<false>(e, n_triangles); }
-
-extern "C++" {
-namespace {
-template <bool COLOUR>
-int mesh_complete(dsr_engine *e, uint64_t *n_triangles) {
-  // (no deferred render is queued here: it reads the scene, as this call does, and stays pending)
-  CHECK_E_NOFLUSH(e);
-  int st = mesh_release(e);
-  if (st) return st;
-  if (n_triangles) *n_triangles = 0;
-  // Everything this call writes is its own: the list, the tile sums and — through a copy of the scene's parameters — the
-  // counters the scans leave their totals in.  The engine's scratch and counters keep what the last frame left.
-  MeshScratch scratch;
-  SceneP sc = e->scene;
-  int2 *tileSums = nullptr;
-  int32_t *list = nullptr;
-  if ((st = scratch.get(&sc.ctr, (size_t)CTR_COUNT)) || (st = scratch.get(&tileSums, (size_t)e->numTilesE)) ||
-      (st = scratch.get(&list, (size_t)e->E)))
-    return st;
-  HIP_TRY(hipMemsetAsync(sc.ctr, 0, CTR_COUNT * 4, e->stream));
-  LAUNCH(e, "mesh_candidates", k_owning_count, dim3(e->numTilesE), dim3(kTileThreads), sc, e->E, tileSums);
-  LAUNCH(e, "scan_tiles", k_scan_tile_sums, dim3(1), dim3(1024), tileSums, e->numTilesE, sc, (int)SCAN_NCAND, e->E);
-  LAUNCH(e, "mesh_candidates", k_owning_write, dim3(e->numTilesE), dim3(kTileThreads), sc, e->E, (const int2 *)tileSums, list, e->E);
-  const int32_t *nPtr = sc.ctr + CTR_DECAY_NCAND;
-  int32_t head[2] = {0, 0};  // list length; host slots handed out (an upper bound of the stored entries)
-  HIP_TRY(hipMemcpyAsync(&head[0], nPtr, 4, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(&head[1], e->scene.ctr + CTR_HOST_USED, 4, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  const int n = head[0];
-  if (n <= 0) return DSR_OK;
-  const unsigned long long cap = (unsigned long long)std::max(e->noBlocks, n) * 32ull - 1ull;
-  if (!e->scene.swapStored) {  // nothing is ever stored: the resident mesher over the same list
-    st = mesh_from_list<MeshResident, COLOUR>(e, sc, list, nPtr, n, tileSums, cap, n, no_prep);
-  } else {
-    if (head[1] < 0 || head[1] > host_store_slots(e)) return fail(DSR_E_DEVICE, "host store inconsistent");
-    // The pool: a chunk of the list reaches at most 8 entries per listed one, and never more than the store holds.  A chunk of
-    // 2^17 entries bounds it at 1 GiB; a map with fewer stored entries than that takes ONE chunk whatever its size, and only a
-    // mesh of several chunks fetches planes twice (count pass, write pass).  env DSR_MESH_CHUNK: the chunk (tests).  With colours a
-    // plane of the pool is a slot of 3 KiB (sdf + colour words), so a third of that chunk keeps the bound.
-    using Pooled = std::conditional_t<COLOUR, MeshPooledColour, MeshPooled>;
-    constexpr size_t kSlot = COLOUR ? kColourSlotBytes : kPlaneBytes;
-    int chunk = (1 << 17) / (int)(kSlot / kPlaneBytes);
-    if (const char *c = getenv("DSR_MESH_CHUNK")) chunk = std::max(1, atoi(c));
-    if (head[1] <= 8ll * chunk) chunk = std::max(chunk, n);
-    const int poolCap = (int)std::min<long long>(head[1], 8ll * std::min(chunk, n));
-    int32_t *planeOf = nullptr, *poolIds = nullptr, *poolCtr = nullptr;
-    uint8_t *pool = nullptr;
-    if ((st = scratch.get(&planeOf, (size_t)e->E)) || (st = scratch.get(&poolIds, (size_t)poolCap)) ||
-        (st = scratch.get(&poolCtr, 2)) || (st = scratch.get(&pool, (size_t)poolCap * kSlot)))
-      return st;
-    MeshP mp; mp.voxelSize = e->s.voxel_size; mp.hashMask = (uint32_t)(e->noBuckets - 1); mp.noBuckets = e->noBuckets;
-    const int noSlots = (int)std::min<long long>(host_store_slots(e), 0x7fffffff);
-    HIP_TRY(hipMemsetAsync(poolCtr, 0, 8, e->stream));  // (the overflow flag, poolCtr[1], is sticky over the chunks)
-    auto prep = [&](int first, int end, Pooled &src) -> int {
-      src.planeOf = planeOf; src.pool = pool; src.firstItem = first; src.endItem = end;
-      HIP_TRY(hipMemsetAsync(planeOf, 0xff, (size_t)e->E * 4, e->stream));
-      HIP_TRY(hipMemsetAsync(poolCtr, 0, 4, e->stream));
-      LAUNCH(e, "mesh_mark", k_mesh_mark, dim3(div_up((long long)(end - first) * 8, 256)), dim3(256), sc, mp, (const int32_t *)list,
-             nPtr, first, end, planeOf, poolIds, poolCap, poolCtr);
-      LAUNCH(e, "mesh_gather", (k_mesh_gather<COLOUR>), dim3(std::max(1, std::min(1024, div_up(poolCap, 4)))), dim3(256), sc, (int)e->s.max_w,
-             e->noBlocks, noSlots, (const int32_t *)poolIds, (const int32_t *)poolCtr, poolCap, pool);
-      return DSR_OK;
-    };
-    st = mesh_from_list<Pooled, COLOUR>(e, sc, list, nPtr, n, tileSums, cap, chunk, prep);
-    if (st == DSR_OK) {
-      int32_t over = 0;
-      HIP_TRY(hipMemcpy(&over, poolCtr + 1, 4, hipMemcpyDeviceToHost));
-      if (over) { (void)mesh_release(e); return fail(DSR_E_DEVICE, "mesh plane pool overflow"); }
-    }
-  }
-  if (st == DSR_OK && n_triangles) *n_triangles = e->meshCount;
-  return st;
-}
-}  // namespace
-}  // extern "C++"
-
-int dsr_save_scene_to_mesh_complete(dsr_engine *e, const char *path) {
-  int st = dsr_mesh_scene_complete(e, nullptr);
-  if (st == DSR_OK) st = dsr_mesh_write_obj(e, path);
-  if (e) (void)mesh_release(e);
-  return st;
-}
-
-int dsr_dump_merged_block(dsr_engine *e, int entry, dsr_voxel *out, int *present) {
-  CHECK_E_NOFLUSH(e);
-  if (!present || entry < 0 || entry >= e->E) return fail(DSR_E_ARG, "bad entry");
-  *present = 0;
-  MeshScratch scratch;
-  uint8_t *blk = nullptr;
-  int32_t *flag = nullptr;
-  int st;
-  if ((st = scratch.get(&blk, (size_t)kBlockBytes)) || (st = scratch.get(&flag, 1))) return st;
-  const int noSlots = (int)std::min<long long>(host_store_slots(e), 0x7fffffff);
-  LAUNCH(e, "merged_block", k_merged_block, dim3(1), dim3(64), e->scene, (int)e->s.max_w, e->noBlocks, noSlots, entry, blk, flag);
-  std::vector<uint8_t> b(kBlockBytes);
-  int32_t f = 0;
-  HIP_TRY(hipMemcpyAsync(&f, flag, 4, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(b.data(), blk, kBlockBytes, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  if (!f) return DSR_OK;
-  *present = 1;
-  for (int v = 0; out && v < kBlockSize3; ++v) {
-    dsr_voxel o; memset(&o, 0, sizeof o);
-    memcpy(&o.sdf, b.data() + kOffSdf + v * 2, 2);
-    o.w_depth = b[kOffWDepth + v]; o.w_color = b[kOffClr + v * 4 + 3];
-    o.clr[0] = b[kOffClr + v * 4]; o.clr[1] = b[kOffClr + v * 4 + 1]; o.clr[2] = b[kOffClr + v * 4 + 2];
-    out[v] = o;
-  }
-  return DSR_OK;
-}
-
-int dsr_mesh_get(dsr_engine *e, dsr_triangle *out, uint64_t first, uint64_t count) {
-  CHECK_E(e);
-  if (!out && count) return fail(DSR_E_ARG, "null");
-  if (first + count > e->meshCount) return fail(DSR_E_ARG, "triangle range outside the mesh");
-  if (count) {
-    HIP_TRY(hipMemcpyAsync(out, e->meshTris + first, (size_t)count * sizeof(dsr_triangle), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-  }
-  return DSR_OK;
-}
-
-// ITMMesh::WriteOBJ
-int dsr_mesh_write_obj(dsr_engine *e, const char *path) {
-  CHECK_E(e);
-  if (!path) return fail(DSR_E_ARG, "null path");
-  FILE *f = fopen(path, "w+");
-  if (!f) return fail(DSR_E_ARG, "cannot open the OBJ file for writing");
-  const uint64_t chunk = 1u << 20;
-  std::vector<dsr_triangle> buf((size_t)std::min<uint64_t>(chunk, e->meshCount));
-  int st = DSR_OK;
-  for (uint64_t first = 0; first < e->meshCount && st == DSR_OK; first += chunk) {
-    const uint64_t cnt = std::min<uint64_t>(chunk, e->meshCount - first);
-    st = dsr_mesh_get(e, buf.data(), first, cnt);
-    for (uint64_t i = 0; i < cnt && st == DSR_OK; ++i) {
-      const dsr_triangle &t = buf[(size_t)i];
-      fprintf(f, "v %f %f %f\n", t.p0[0], t.p0[1], t.p0[2]);
-      fprintf(f, "v %f %f %f\n", t.p1[0], t.p1[1], t.p1[2]);
-      fprintf(f, "v %f %f %f\n", t.p2[0], t.p2[1], t.p2[2]);
-    }
-  }
-  for (uint64_t i = 0; i < e->meshCount && st == DSR_OK; i++)
-    fprintf(f, "f %llu %llu %llu\n", (unsigned long long)(i * 3 + 2 + 1), (unsigned long long)(i * 3 + 1 + 1),
-            (unsigned long long)(i * 3 + 0 + 1));
-  fclose(f);
-  return st;
-}
-
-// ITMMainEngine::SaveSceneToMesh
-int dsr_save_scene_to_mesh(dsr_engine *e, const char *path) {
-  int st = dsr_mesh_scene(e, nullptr);
-  if (st == DSR_OK) st = dsr_mesh_write_obj(e, path);
-  if (e) (void)dsr_mesh_free(e);
-  return st;
-}
-
-// ---- coloured meshes (include/dsr_mesh.h; builder-defined)
-
-int dsr_mesh_scene_coloured(dsr_engine *e, int complete, uint64_t *n_triangles) {
-  const int st = complete ? mesh_complete<true>(e, n_triangles) : mesh_resident<true>(e, n_triangles);
-  if (st == DSR_OK) e->meshColoured = true;  // (also a mesh of no triangles: get_colours(0, 0) and the PLY header treat it as coloured)
-  return st;
-}
-
-int dsr_mesh_get_colours(dsr_engine *e, dsr_triangle_colour *out, uint64_t first, uint64_t count) {
-  CHECK_E(e);
-  if (!out && count) return fail(DSR_E_ARG, "null");
-  if (!e->meshColoured)
-    return fail(DSR_E_ARG, e->meshCount ? "the current mesh has no colours (dsr_mesh_scene_coloured makes one that has)" : "no mesh");
-  if (first + count > e->meshCount) return fail(DSR_E_ARG, "triangle range outside the mesh");
-  if (count) {
-    HIP_TRY(hipMemcpyAsync(out, e->meshClr + first, (size_t)count * sizeof(dsr_triangle_colour), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-  }
-  return DSR_OK;
-}
-
-extern "C++" {
-namespace {
-// the current mesh, chunk by chunk: geometry and (wantColours) colours of triangles first .. first + cnt - 1 to `emit`
-template <class EMIT>
-int mesh_for_each_chunk(dsr_engine *e, bool wantColours, EMIT emit) {
-  const uint64_t chunk = 1u << 20;
-  std::vector<dsr_triangle> tris((size_t)std::min<uint64_t>(chunk, e->meshCount));
-  std::vector<dsr_triangle_colour> clrs(wantColours ? tris.size() : 0);
-  int st = DSR_OK;
-  for (uint64_t first = 0; first < e->meshCount && st == DSR_OK; first += chunk) {
-    const uint64_t cnt = std::min<uint64_t>(chunk, e->meshCount - first);
-    st = dsr_mesh_get(e, tris.data(), first, cnt);
-    if (st == DSR_OK && wantColours) st = dsr_mesh_get_colours(e, clrs.data(), first, cnt);
-    if (st == DSR_OK) emit(tris.data(), wantColours ? clrs.data() : nullptr, cnt);
-  }
-  return st;
-}
-bool ends_in_ply(const char *path) {
-  const size_t n = strlen(path);
-  return n >= 4 && path[n - 4] == '.' && (path[n - 3] | 0x20) == 'p' && (path[n - 2] | 0x20) == 'l' && (path[n - 1] | 0x20) == 'y';
-}
-}  // namespace
-}  // extern "C++"
-
-int dsr_mesh_write_obj_coloured(dsr_engine *e, const char *path) {
-  CHECK_E(e);
-  if (!path) return fail(DSR_E_ARG, "null path");
-  if (!e->meshColoured)
-    return fail(DSR_E_ARG, e->meshCount ? "the current mesh has no colours (dsr_mesh_scene_coloured makes one that has)" : "no mesh");
-  FILE *f = fopen(path, "w+");
-  if (!f) return fail(DSR_E_ARG, "cannot open the OBJ file for writing");
-  int st = mesh_for_each_chunk(e, true, [&](const dsr_triangle *t, const dsr_triangle_colour *c, uint64_t cnt) {
-    for (uint64_t i = 0; i < cnt; ++i) {
-      const float *p[3] = {t[i].p0, t[i].p1, t[i].p2};
-      const uint8_t *q[3] = {c[i].c0, c[i].c1, c[i].c2};
-      for (int k = 0; k < 3; ++k)
-        fprintf(f, "v %f %f %f %f %f %f\n", p[k][0], p[k][1], p[k][2], (float)q[k][0] / 255.0f, (float)q[k][1] / 255.0f,
-                (float)q[k][2] / 255.0f);
-    }
-  });
-  for (uint64_t i = 0; i < e->meshCount && st == DSR_OK; i++)
-    fprintf(f, "f %llu %llu %llu\n", (unsigned long long)(i * 3 + 2 + 1), (unsigned long long)(i * 3 + 1 + 1),
-            (unsigned long long)(i * 3 + 0 + 1));
-  const bool bad = ferror(f) != 0;
-  if ((fclose(f) != 0 || bad) && st == DSR_OK) st = fail(DSR_E_ARG, "writing the OBJ file failed");
-  return st;
-}
-
-int dsr_mesh_write_ply(dsr_engine *e, const char *path) {
-  CHECK_E(e);
-  if (!path) return fail(DSR_E_ARG, "null path");
-  const bool colours = e->meshColoured;
-  const uint64_t n = e->meshCount;
-  if (n * 3 > 0x7fffffffull) return fail(DSR_E_ARG, "too many vertices for the int indices of a PLY face");
-  FILE *f = fopen(path, "wb");
-  if (!f) return fail(DSR_E_ARG, "cannot open the PLY file for writing");
-  fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %llu\nproperty float x\nproperty float y\nproperty float z\n",
-          (unsigned long long)(n * 3));
-  if (colours) fprintf(f, "property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\n");
-  fprintf(f, "element face %llu\nproperty list uchar int vertex_indices\nend_header\n", (unsigned long long)n);
-  std::vector<uint8_t> rec;
-  int st = mesh_for_each_chunk(e, colours, [&](const dsr_triangle *t, const dsr_triangle_colour *c, uint64_t cnt) {
-    const size_t vb = colours ? 16 : 12;
-    rec.resize((size_t)cnt * 3 * vb);
-    for (uint64_t i = 0; i < cnt; ++i) {
-      const float *p[3] = {t[i].p0, t[i].p1, t[i].p2};
-      for (int k = 0; k < 3; ++k) {
-        uint8_t *o = rec.data() + ((size_t)i * 3 + k) * vb;
-        memcpy(o, p[k], 12);
-        if (colours) memcpy(o + 12, k == 0 ? c[i].c0 : (k == 1 ? c[i].c1 : c[i].c2), 4);
-      }
-    }
-    fwrite(rec.data(), 1, rec.size(), f);
-  });
-  const uint64_t faceChunk = 1u << 16;
-  rec.resize((size_t)std::min<uint64_t>(faceChunk, n) * 13);
-  for (uint64_t first = 0; first < n && st == DSR_OK; first += faceChunk) {
-    const uint64_t cnt = std::min<uint64_t>(faceChunk, n - first);
-    for (uint64_t i = 0; i < cnt; ++i) {
-      uint8_t *o = rec.data() + (size_t)i * 13;
-      const int32_t idx[3] = {(int32_t)((first + i) * 3 + 2), (int32_t)((first + i) * 3 + 1), (int32_t)((first + i) * 3)};
-      o[0] = 3;
-      memcpy(o + 1, idx, 12);
-    }
-    fwrite(rec.data(), 1, (size_t)cnt * 13, f);
-  }
-  const bool bad = ferror(f) != 0;
-  if ((fclose(f) != 0 || bad) && st == DSR_OK) st = fail(DSR_E_ARG, "writing the PLY file failed");
-  return st;
-}
-
-int dsr_save_scene_to_mesh_coloured(dsr_engine *e, const char *path, int complete) {
-  if (e && !path) return fail(DSR_E_ARG, "null path");
-  int st = dsr_mesh_scene_coloured(e, complete, nullptr);
-  if (st == DSR_OK) st = ends_in_ply(path) ? dsr_mesh_write_ply(e, path) : dsr_mesh_write_obj_coloured(e, path);
-  if (e) (void)mesh_release(e);
-  return st;
-}
-
-// ---- indexed meshes (include/dsr_mesh.h, k_mesh_indexed.h; builder-defined).  The launches; the entry points
-// are dsr_mesh_indexed.hip's.
-
-extern "C++" {
-namespace {
-// Count per block (used edges, triangles), two scans, ONE read-back of both totals, exact buffers, then per chunk the vertex and the
-// index pass.  prep as in mesh_from_list, with pool planes for the 27 blocks a lattice touches.  Into e->imesh (released by the caller).
-template <class SRC, bool COLOUR, class PREP>
-int mesh_indexed_from_list(dsr_engine *e, const SceneP &sc, const int32_t *list, const int32_t *nPtr, int n, int2 *tileSums, int chunk,
-                           bool normals, PREP prep) {
-  MeshScratch scratch;
-  uint32_t *vCount = nullptr, *tCount = nullptr, *vBase = nullptr, *tBase = nullptr;
-  uint2 *laneInfo = nullptr;
-  int32_t *posOf = nullptr, *totals = nullptr;
-  int st;
-  if ((st = scratch.get(&vCount, (size_t)n)) || (st = scratch.get(&tCount, (size_t)n)) || (st = scratch.get(&vBase, (size_t)n)) ||
-      (st = scratch.get(&tBase, (size_t)n)) || (st = scratch.get(&laneInfo, (size_t)n * 64)) || (st = scratch.get(&posOf, (size_t)e->E)) ||
-      (st = scratch.get(&totals, (size_t)2 * CTR_COUNT)))
-    return st;
-  MeshP mp; mp.voxelSize = e->s.voxel_size; mp.hashMask = (uint32_t)(e->noBuckets - 1); mp.noBuckets = e->noBuckets;
-  const int tiles = div_up(n, kTile);
-  const bool oneChunk = n <= chunk;
-  auto grid = [](int items) { return dim3(std::min(8192, div_up(items, kMeshWaves))); };
-  SRC src{};
-  for (int first = 0; first < n; first += chunk) {
-    const int end = (int)std::min<long long>((long long)first + chunk, n);
-    if ((st = prep(first, end, src))) return st;
-    LAUNCH(e, "mesh_indexed_count", (k_mesh_indexed_count<SRC>), grid(end - first), dim3(64 * kMeshWaves), sc, mp, list, nPtr, laneInfo,
-           vCount, tCount, src);
-  }
-  // (the scans leave their totals in CTR_MESH_TOTAL of the counters they are given: two sets of this call's own)
-  HIP_TRY(hipMemsetAsync(totals, 0, 2 * CTR_COUNT * 4, e->stream));
-  for (int k = 0; k < 2; ++k) {
-    SceneP scK = sc;
-    scK.ctr = totals + k * CTR_COUNT;
-    const uint32_t *count = k ? tCount : vCount;
-    LAUNCH(e, "mesh_scan", k_u32_tile_sums, dim3(tiles), dim3(kTileThreads), count, nPtr, tileSums);
-    LAUNCH(e, "scan_tiles", k_scan_tile_sums, dim3(1), dim3(1024), tileSums, tiles, scK, (int)SCAN_MESH, 0);
-    LAUNCH(e, "mesh_scan", k_u32_tile_offsets, dim3(tiles), dim3(kTileThreads), count, nPtr, (const int2 *)tileSums, k ? tBase : vBase);
-  }
-  HIP_TRY(hipMemsetAsync(posOf, 0xff, (size_t)e->E * 4, e->stream));
-  LAUNCH(e, "mesh_indexed_positions", k_mesh_list_positions, dim3(std::min(1024, div_up(n, 256))), dim3(256), list, nPtr, posOf);
-  int32_t host[2 * CTR_COUNT];
-  HIP_TRY(hipMemcpyAsync(host, totals, sizeof host, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  const int nv = host[CTR_MESH_TOTAL], nt = host[CTR_COUNT + CTR_MESH_TOTAL];
-  if (nv < 0 || nt < 0) return fail(DSR_E_ARG, "indexed mesh has more than 2^31 - 1 vertices or triangles");
-  dsr_engine::IndexedMesh &m = e->imesh;
-  auto alloc = [&](auto **p, size_t count) {
-    return count == 0 || hipMalloc(reinterpret_cast<void **>(p), count * 4) == hipSuccess;
-  };
-  if (!alloc(&m.verts, (size_t)nv * 3) || !alloc(&m.indices, (size_t)nt * 3) || (normals && !alloc(&m.normals, (size_t)nv * 3)) ||
-      (COLOUR && !alloc(&m.colours, (size_t)nv))) {
-    (void)hipGetLastError();
-    return fail(DSR_E_NOMEM, "indexed mesh buffer allocation failed");
-  }
-  if (nv > 0 || nt > 0) {
-    for (int first = 0; first < n && st == DSR_OK; first += chunk) {
-      const int end = (int)std::min<long long>((long long)first + chunk, n);
-      if (!oneChunk && (st = prep(first, end, src))) break;
-      LAUNCH(e, "mesh_indexed_vertices", (k_mesh_indexed_vertices<SRC, COLOUR>), grid(end - first), dim3(64 * kMeshWaves), sc, mp, list,
-             nPtr, (const uint2 *)laneInfo, (const uint32_t *)vBase, m.verts, m.normals, m.colours, (unsigned long long)nv, src);
-      LAUNCH(e, "mesh_indexed_indices", (k_mesh_indexed_indices<SRC>), grid(end - first), dim3(64 * kMeshWaves), sc, mp, list, nPtr,
-             (const uint2 *)laneInfo, (const uint32_t *)vBase, (const uint32_t *)tBase, (const int32_t *)posOf, m.indices,
-             (unsigned long long)nt, src);
-    }
-  }
-  const hipError_t err = hipStreamSynchronize(e->stream);  // (also before the scratch goes)
-  if (st == DSR_OK && err != hipSuccess) st = fail(DSR_E_DEVICE, hipGetErrorString(err));
-  if (st == DSR_OK) { m.nVerts = (uint64_t)nv; m.nTris = (uint64_t)nt; }
-  return st;
-}
-template <class SRC> int no_prep_any(int, int, SRC &) { return DSR_OK; }
-}  // namespace
-}  // extern "C++"
-
-extern "C++" int dsr_internal::engine_mesh_indexed_release(dsr_engine *e) {
-  dsr_engine::IndexedMesh &m = e->imesh;
-  if (m.verts || m.normals || m.colours || m.indices) HIP_TRY(hipStreamSynchronize(e->stream));
-  for (void *p : {(void *)m.verts, (void *)m.normals, (void *)m.colours, (void *)m.indices})
-    if (p) (void)hipFree(p);
-  m = dsr_engine::IndexedMesh{};
-  return DSR_OK;
-}
-
-// Everything this call writes is its own, with and without DSR_MESH_COMPLETE: the list, the tile sums, the counters the scans use.
-extern "C++" int dsr_internal::engine_mesh_indexed(dsr_engine *e, int flags) {
-  int st = engine_mesh_indexed_release(e);
-  if (st) return st;
-  const bool complete = (flags & DSR_MESH_COMPLETE) != 0, colours = (flags & DSR_MESH_COLOURS) != 0, normals = (flags & DSR_MESH_NORMALS) != 0;
-  MeshScratch scratch;
-  SceneP sc = e->scene;
-  int2 *tileSums = nullptr;
-  int32_t *list = nullptr;
-  if ((st = scratch.get(&sc.ctr, (size_t)CTR_COUNT)) || (st = scratch.get(&tileSums, (size_t)e->numTilesE)) ||
-      (st = scratch.get(&list, (size_t)e->E)))
-    return st;
-  HIP_TRY(hipMemsetAsync(sc.ctr, 0, CTR_COUNT * 4, e->stream));
-  if (complete) LAUNCH(e, "mesh_candidates", k_owning_count, dim3(e->numTilesE), dim3(kTileThreads), sc, e->E, tileSums);
-  else LAUNCH(e, "mesh_candidates", k_allocated_count, dim3(e->numTilesE), dim3(kTileThreads), sc, e->E, tileSums);
-  LAUNCH(e, "scan_tiles", k_scan_tile_sums, dim3(1), dim3(1024), tileSums, e->numTilesE, sc, (int)SCAN_NCAND, e->E);
-  if (complete) LAUNCH(e, "mesh_candidates", k_owning_write, dim3(e->numTilesE), dim3(kTileThreads), sc, e->E, (const int2 *)tileSums, list, e->E);
-  else LAUNCH(e, "mesh_candidates", k_allocated_write, dim3(e->numTilesE), dim3(kTileThreads), sc, e->E, (const int2 *)tileSums, list, e->E);
-  const int32_t *nPtr = sc.ctr + CTR_DECAY_NCAND;
-  int32_t head[2] = {0, 0};  // list length; host slots handed out (an upper bound of the stored entries)
-  HIP_TRY(hipMemcpyAsync(&head[0], nPtr, 4, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(&head[1], e->scene.ctr + CTR_HOST_USED, 4, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  const int n = head[0];
-  dsr_engine::IndexedMesh &m = e->imesh;
-  if (n > 0) {
-    if (!complete || !e->scene.swapStored) {
-      st = colours ? mesh_indexed_from_list<MeshResident, true>(e, sc, list, nPtr, n, tileSums, n, normals, no_prep_any<MeshResident>)
-                   : mesh_indexed_from_list<MeshResident, false>(e, sc, list, nPtr, n, tileSums, n, normals, no_prep_any<MeshResident>);
-    } else {
-      if (head[1] < 0 || head[1] > host_store_slots(e)) return fail(DSR_E_DEVICE, "host store inconsistent");
-      // The pool, as mesh_complete's — but the lattice of a listed entry now touches 27 blocks.  The pool is sized by the DISTINCT
-      // planes a chunk can need: never more than the store holds, and never more than 27 per listed entry.
-      const size_t slotBytes = colours ? kColourSlotBytes : kPlaneBytes;
-      int chunk = (1 << 17) / (int)(slotBytes / kPlaneBytes);
-      if (const char *c = getenv("DSR_MESH_CHUNK")) chunk = std::max(1, atoi(c));
-      if (head[1] <= 8ll * chunk) chunk = std::max(chunk, n);
-      const int poolCap = (int)std::min<long long>(head[1], 27ll * std::min(chunk, n));
-      int32_t *planeOf = nullptr, *poolIds = nullptr, *poolCtr = nullptr;
-      uint8_t *pool = nullptr;
-      if ((st = scratch.get(&planeOf, (size_t)e->E)) || (st = scratch.get(&poolIds, (size_t)poolCap)) ||
-          (st = scratch.get(&poolCtr, 2)) || (st = scratch.get(&pool, (size_t)poolCap * slotBytes)))
-        return st;
-      MeshP mp; mp.voxelSize = e->s.voxel_size; mp.hashMask = (uint32_t)(e->noBuckets - 1); mp.noBuckets = e->noBuckets;
-      const int noSlots = (int)std::min<long long>(host_store_slots(e), 0x7fffffff);
-      HIP_TRY(hipMemsetAsync(poolCtr, 0, 8, e->stream));
-      auto prep = [&](int first, int end, auto &src) -> int {
-        src.planeOf = planeOf; src.pool = pool; src.firstItem = first; src.endItem = end;
-        HIP_TRY(hipMemsetAsync(planeOf, 0xff, (size_t)e->E * 4, e->stream));
-        HIP_TRY(hipMemsetAsync(poolCtr, 0, 4, e->stream));
-        LAUNCH(e, "mesh_mark", k_mesh_mark27, dim3(div_up((long long)(end - first) * 27, 256)), dim3(256), sc, mp, (const int32_t *)list,
-               nPtr, first, end, planeOf, poolIds, poolCap, poolCtr);
-        if (colours)
-          LAUNCH(e, "mesh_gather", (k_mesh_gather<true>), dim3(std::max(1, std::min(1024, div_up(poolCap, 4)))), dim3(256), sc,
-                 (int)e->s.max_w, e->noBlocks, noSlots, (const int32_t *)poolIds, (const int32_t *)poolCtr, poolCap, pool);
-        else
-          LAUNCH(e, "mesh_gather", (k_mesh_gather<false>), dim3(std::max(1, std::min(1024, div_up(poolCap, 4)))), dim3(256), sc,
-                 (int)e->s.max_w, e->noBlocks, noSlots, (const int32_t *)poolIds, (const int32_t *)poolCtr, poolCap, pool);
-        return DSR_OK;
-      };
-      st = colours ? mesh_indexed_from_list<MeshPooledColour, true>(e, sc, list, nPtr, n, tileSums, chunk, normals, prep)
-                   : mesh_indexed_from_list<MeshPooled, false>(e, sc, list, nPtr, n, tileSums, chunk, normals, prep);
-      if (st == DSR_OK) {
-        int32_t over = 0;
-        HIP_TRY(hipMemcpy(&over, poolCtr + 1, 4, hipMemcpyDeviceToHost));
-        if (over) st = fail(DSR_E_DEVICE, "mesh plane pool overflow");
-      }
-    }
-  }
-  if (st != DSR_OK) { (void)engine_mesh_indexed_release(e); return st; }
-  m.flags = flags;
-  m.valid = true;
   return DSR_OK;
 }
 

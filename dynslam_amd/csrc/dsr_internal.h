@@ -1,5 +1,5 @@
 // dsr_internal.h — what the translation units of libdsr_hip.so share (NOT part of the C ABI: include/dsr.h is):
-//   dsr_engine.hip    the engine — creation, allocation, integration, GC, swapping, raycast / render, the volume batch, meshing, dumps
+//   dsr_engine.hip    the engine — creation, allocation, integration, GC, swapping, raycast / render, the volume batch, dumps
 //   dsr_view.hip      the view and the edges of the path — frames in, the view pipeline, the instance view split, layout conversions,
 //                     depth ingest, the two previews
 //   dsr_exchange.hip  the multi-GPU layer exchange (RCCL, loaded on first use) and the compositing entry points
@@ -11,8 +11,8 @@
 //   dsr_merge.hip     folding one volume into another at a rigid pose (include/dsr_merge.h): candidates, ordered insert, the pull;
 //                     and, on the same device functions and insert, a volume resampled into a dense grid and back (include/dsr_dense.h)
 //   dsr_align.hip     aligning one volume to another, SDF to SDF (include/dsr_align.h): the list of blocks, the queued evaluations
-//   dsr_mesh_indexed.hip  the indexed mesh's entry points (include/dsr_mesh.h): flags, getters, the PLY / OBJ writers.  Host code only:
-//                     its kernels (k_mesh_indexed.h) build on the mesher's policies and scans, so dsr_engine.hip holds their launches
+//   dsr_mesh.hip      meshing (include/dsr.h, include/dsr_mesh.h): the soup mesh — resident, complete, coloured — and the indexed mesh;
+//                     their list step, plane pool and chunk loop, the read-backs, the OBJ / PLY writers, dsr_dump_merged_block
 //   dsr_esdf.hip      an exact Euclidean signed distance field from a dense grid (include/dsr_esdf.h): the checks, three launches
 // Every KERNEL header (k_*.h) is included by exactly ONE of them: __global__ kernels have external linkage.  Headers that hold only
 // inline device functions (dsr_device.h, dsr_math.h, dsr_sample.h) are shared: any unit may include them.
@@ -350,26 +350,33 @@ extern std::atomic<int> g_enginesOnDevice[64];  // live engines per device (rang
 int engine_set_device(dsr_engine *e);
 int engine_flush_deferred(dsr_engine *e);  // queue what dsr_prepare / dsr_batch_fuse deferred (paired render)
 void engine_prof_resolve(dsr_engine *e);
-// ... for dsr_snapshot.hip: ResetScene; the ascending list of allocated entries into e->decayCand with its length in
-// ctr[CTR_DECAY_NCAND] (the list kernels of Decay(forceAll) and meshing); the GC ring grown to `slots` planes; one more slab of the
-// host store; the words of SceneP::allocBits; is the engine a volume or the source of a batch that is still alive?
+// ... the ordered list of a scene's entries, by the engine's list kernels (count, scan, write) under the profile label `label`: every
+// allocated entry or (owning) every entry that owns voxel data, ascending, into out[0 .. capacity); its length, capped at capacity,
+// lands in counter lengthCtr of sc (CTR_DECAY_NCAND or CTR_NO_ALLOCATED).  tileSums: e->numTilesE elements.  Decay(forceAll), the free
+// view's list, a snapshot and the meshers (dsr_mesh.hip) all list through this
+void engine_list_entries(dsr_engine *e, const char *label, bool owning, const SceneP &sc, int2 *tileSums, int32_t *out, int capacity,
+                         int lengthCtr = CTR_DECAY_NCAND);
+// ... for dsr_mesh.hip: exclusive offsets of the *nPtr (host's view of it: n) u32 counts, their total left in CTR_MESH_TOTAL of sc's
+// counters.  tileSums: div_up(n, kTile) elements
+void engine_scan_counts(dsr_engine *e, const SceneP &sc, const uint32_t *counts, const int32_t *nPtr, int n, int2 *tileSums,
+                        uint32_t *offsets);
+// ... for dsr_snapshot.hip: ResetScene; the GC ring grown to `slots` planes; one more slab of the host store; the words of
+// SceneP::allocBits; is the engine a volume or the source of a batch that is still alive?
 int engine_reset(dsr_engine *e);
-int engine_list_allocated(dsr_engine *e);
 int engine_ensure_fifo(dsr_engine *e, int slots);
 int engine_add_host_slab(dsr_engine *e);
 int engine_small_bit_words();
 bool engine_in_live_batch(dsr_engine *e);
 int engine_render(dsr_engine *e, int type, const float pose_m[16], const float intrinsics[4], void *rgba_out, void *depth_out,
                   bool outIsDevice);
-// ... for dsr_mesh_indexed.hip: build the indexed mesh into e->imesh (flags checked by the caller; any earlier one is released
-// first), release it
-int engine_mesh_indexed(dsr_engine *e, int flags);
-int engine_mesh_indexed_release(dsr_engine *e);
+// dsr_mesh.hip: release the soup mesh (meshTris, meshClr; what dsr_mesh_free does behind its entry check) — a snapshot load replaces
+// the state it was made from
+int mesh_release(dsr_engine *e);
 // dsr_hostio.hip: is [p, p + bytes) inside a range the caller page-locked through dsr_pin_host_buffer?
 bool host_range_pinned(const void *p, size_t bytes);
 // dsr_profile.hip: div_short(x, b) == x / b for every x? (k_integrate.h; checked once per engine for its mu)
 int short_division_exact(hipStream_t stream, float b, bool *exact);
-// ---- shared by the calls that read one volume against another (dsr_merge.hip, dsr_align.hip)
+// ---- shared by the calls that read one volume against another (dsr_merge.hip, dsr_align.hip); Scratch also by the meshers
 struct Scratch {  // everything such a call allocates; freed when it leaves
   const char *what;  // the message of DSR_E_NOMEM
   std::vector<void *> ptrs;

@@ -204,7 +204,8 @@ int save_impl(dsr_engine *e, const char *path, dsr_snapshot **out) {
   int32_t *nOwnedSeen = reinterpret_cast<int32_t *>(reinterpret_cast<uint8_t *>(cnt) + sizeof(Counters));
   HIP_TRY(hipMemcpyAsync(cnt->ctr, e->scene.ctr, sizeof cnt->ctr, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipMemcpyAsync(cnt->work, e->scene.work, sizeof cnt->work, hipMemcpyDeviceToHost, e->stream));
-  { int st = engine_list_allocated(e); if (st) return st; }
+  engine_list_entries(e, "snapshot_candidates", false, e->scene, e->tileSums, e->decayCand, e->noBlocks);
+  HIP_TRY(hipGetLastError());
   const int32_t *nPtr = e->scene.ctr + CTR_DECAY_NCAND;
   HIP_TRY(hipMemcpyAsync(nOwnedSeen, nPtr, 4, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
@@ -537,10 +538,7 @@ int load_impl(dsr_engine *e, const char *path, const dsr_snapshot *snap) {
   if (e->sideStream) HIP_TRY(hipStreamSynchronize(e->sideStream));
   e->sidePending = false;
   if (e->device >= 0 && e->device < 64 && g_ioStream[e->device]) HIP_TRY(hipStreamSynchronize(g_ioStream[e->device]));
-  if (e->meshTris) { (void)hipFree(e->meshTris); e->meshTris = nullptr; }
-  if (e->meshClr) { (void)hipFree(e->meshClr); e->meshClr = nullptr; }
-  e->meshColoured = false;
-  e->meshCount = 0;
+  { int st = mesh_release(e); if (st) return st; }
   { int st = engine_reset(e); if (st) return st; }
 
   Chunks chunks;

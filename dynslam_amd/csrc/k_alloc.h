@@ -288,6 +288,39 @@ __global__ __launch_bounds__(1024) void k_scan_tile_sums(int2 *__restrict__ tile
   scan_tile_sums_body<1024>(tileSums, numTiles, s, mode, capacity, lds);
 }
 
+// ---- exclusive scan of *nPtr u32 counts (the meshers' per-block counts; tiles of kTile): tile sums, k_scan_tile_sums(SCAN_MESH)
+// over them, then the offsets
+__global__ __launch_bounds__(kTileThreads) void k_u32_tile_sums(const uint32_t *__restrict__ v, const int32_t *__restrict__ nPtr,
+                                                                int2 *__restrict__ tileSums) {
+  __shared__ int2 lds[kTileThreads / 64];
+  const int n = *nPtr;
+  const int base = blockIdx.x * kTile + threadIdx.x * kTileItems;
+  int2 c = make_int2(0, 0);
+  for (int j = 0; j < kTileItems; ++j)
+    if (base + j < n) c.x += (int)v[base + j];
+  int2 total;
+  wg_exclusive_scan2<kTileThreads>(c, total, lds);
+  if (threadIdx.x == 0) tileSums[blockIdx.x] = total;
+}
+__global__ __launch_bounds__(kTileThreads) void k_u32_tile_offsets(const uint32_t *__restrict__ v, const int32_t *__restrict__ nPtr,
+                                                                   const int2 *__restrict__ tileOffsets,
+                                                                   uint32_t *__restrict__ out) {
+  __shared__ int2 lds[kTileThreads / 64];
+  const int n = *nPtr;
+  const int base = blockIdx.x * kTile + threadIdx.x * kTileItems;
+  uint32_t a[kTileItems];
+  int2 c = make_int2(0, 0);
+  for (int j = 0; j < kTileItems; ++j) {
+    a[j] = base + j < n ? v[base + j] : 0u;
+    c.x += (int)a[j];
+  }
+  int2 total;
+  const int2 ex = wg_exclusive_scan2<kTileThreads>(c, total, lds);
+  uint32_t run = (uint32_t)(tileOffsets[blockIdx.x].x + ex.x);
+  for (int j = 0; j < kTileItems; ++j)
+    if (base + j < n) { out[base + j] = run; run += a[j]; }
+}
+
 // (Round 4 measured the scan WITHOUT its own launch — the workgroups of the producing sweep draw a ticket, the last one scans:
 //  three launches fewer per instance frame and slower, because every wave pays an agent-scope release, an L2 write-back
 //  (k_alloc_mark 20 -> 124 us).  Archived: profiles/r05_pruned_fold_scans.diff, profiles/r04i_instance_frame_fold_fuse_ab.log.

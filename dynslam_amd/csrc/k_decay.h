@@ -225,12 +225,8 @@ __global__ __launch_bounds__(kTileThreads) void k_decay_commit(SceneP s, const i
     }
 }
 
-// forceAllVoxels: candidates = every entry with ptr >= 0, ascending (ordered compaction).  STORED (k_mesh_complete.h): every entry
-// that owns voxel DATA — resident, or swapped out with a copy in the host store
-template <bool STORED>
-__device__ __forceinline__ bool entry_listed(const SceneP &s, int t) {
-  return s.table[t].ptr >= 0 || (STORED && s.swapStored && s.swapStored[t] != 0);
-}
+// forceAllVoxels: candidates = every entry with ptr >= 0, ascending (ordered compaction).  STORED (the complete meshes): every entry
+// that owns voxel DATA (dsr_device.h entry_listed)
 template <bool STORED>
 __device__ __forceinline__ void allocated_count_body(const SceneP &s, int noTotalEntries, int2 *__restrict__ tileSums, int2 *lds) {
   const int base = blockIdx.x * kTile + threadIdx.x * kTileItems;
@@ -271,6 +267,16 @@ __global__ __launch_bounds__(kTileThreads) void k_allocated_write(SceneP s, int 
                                                                   int32_t *__restrict__ out, int capacity) {
   __shared__ int2 lds[kTileThreads / 64];
   allocated_write_body<false>(s, noTotalEntries, tileOffsets, out, capacity, lds);
+}
+// the ordered list of the entries that own voxel data (entry_listed<true>)
+__global__ __launch_bounds__(kTileThreads) void k_owning_count(SceneP s, int noTotalEntries, int2 *__restrict__ tileSums) {
+  __shared__ int2 lds[kTileThreads / 64];
+  allocated_count_body<true>(s, noTotalEntries, tileSums, lds);
+}
+__global__ __launch_bounds__(kTileThreads) void k_owning_write(SceneP s, int noTotalEntries, const int2 *__restrict__ tileOffsets,
+                                                               int32_t *__restrict__ out, int capacity) {
+  __shared__ int2 lds[kTileThreads / 64];
+  allocated_write_body<true>(s, noTotalEntries, tileOffsets, out, capacity, lds);
 }
 
 // ITMVisualisationEngine::FindVisibleBlocks for a free camera, DENSE: a thread per ALLOCATED entry

@@ -17,26 +17,13 @@
 // a pending merge; MeshPooledColour serves both planes to k_mesh_blocks<true, MeshColoured<MeshPooledColour>>.
 // Nothing here writes the scene: table, swap state, host store and counters are read only.
 #pragma once
-#include "k_decay.h"
 #include "k_mesh.h"
-#include "k_swap.h"
 
 namespace dsr {
 
 constexpr int kPlaneBytes = kBlockSize3 * 2;     // one sdf plane
 constexpr int kClrPlaneBytes = kBlockSize3 * 4;  // one plane of (r, g, b, w_color) words
 constexpr int kColourSlotBytes = kPlaneBytes + kClrPlaneBytes;  // a pool slot of the coloured mesher
-
-// the ordered list of the entries that own voxel data (k_decay.h entry_listed<true>)
-__global__ __launch_bounds__(kTileThreads) void k_owning_count(SceneP s, int noTotalEntries, int2 *__restrict__ tileSums) {
-  __shared__ int2 lds[kTileThreads / 64];
-  allocated_count_body<true>(s, noTotalEntries, tileSums, lds);
-}
-__global__ __launch_bounds__(kTileThreads) void k_owning_write(SceneP s, int noTotalEntries, const int2 *__restrict__ tileOffsets,
-                                                               int32_t *__restrict__ out, int capacity) {
-  __shared__ int2 lds[kTileThreads / 64];
-  allocated_write_body<true>(s, noTotalEntries, tileOffsets, out, capacity, lds);
-}
 
 // does the sdf plane of this (owning) entry have to be built from its stored copy?
 __device__ __forceinline__ bool plane_from_store(const SceneP &s, uint32_t entry, int ptr) {

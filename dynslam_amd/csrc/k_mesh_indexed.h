@@ -10,7 +10,7 @@
 //           edge USED when its ends differ in sign and one of its up to four cells is meshable — for the marching-cubes tables that
 //           is "a triangle references it" (tests/test_mesh_indexed.py proves it over the 256 configurations).  Out: per lane
 //           (mask, used edges in the lower lanes), per block the used edges and the triangles (counted as k_mesh_blocks<false> does);
-//   scan    both per-block counts -> bases (the tile scans of k_mesh.h);
+//   scan    both per-block counts -> bases (the u32 tile scans of k_alloc.h);
 //   vertex  k_mesh_indexed_vertices<SRC, COLOUR>: same staging; every used edge writes position (sdf_interp from the LOWER corner to
 //           the upper, whichever cell asks), normal (SDF gradient, below) and colour (vertex_colour, same orientation) at
 //           base[block] + rank;

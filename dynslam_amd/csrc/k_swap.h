@@ -29,9 +29,7 @@ namespace dsr {
 constexpr int kTransferBlocks = DSR_TRANSFER_BLOCK_NUM;  // SDF_TRANSFER_BLOCK_NUM
 constexpr int kSlabBlocksDefault = 16384;                 // 64 MiB of pinned host memory per slab
 
-__device__ __forceinline__ uint8_t *host_block(const SceneP &s, int slot) {
-  return s.hostSlabs[slot / s.slabBlocks] + (size_t)(slot % s.slabBlocks) * kBlockBytes;
-}
+// (host_block, the address of a host slot, and combine_block_lane, the merge of a stored copy into a block: dsr_device.h)
 
 template <bool OUT>
 __device__ __forceinline__ bool swap_candidate(const SceneP &s, int t, const uint8_t *__restrict__ visType) {
@@ -111,26 +109,6 @@ __global__ __launch_bounds__(256) void k_swapin_fetch(SceneP s, const int32_t *_
     uint4 *dst = reinterpret_cast<uint4 *>(staging + (size_t)i * kBlockBytes);
 #pragma unroll
     for (int k = 0; k < 4; ++k) dst[k * 64 + lane] = src[k * 64 + lane];
-  }
-}
-
-// src (the stored copy) merged into dst, both plane-wise blocks (dsr_device.h combine_voxel_*); this lane's 8 voxels
-__device__ __forceinline__ void combine_block_lane(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, int lane, int maxW) {
-#pragma unroll 1
-  for (int x = 0; x < 8; ++x) {
-    const int v = lane * 8 + x;
-    const int oldW = src[kOffWDepth + v];
-    if (oldW != 0) {  // depth
-      short sdf = *reinterpret_cast<const short *>(dst + kOffSdf + v * 2);
-      int w = dst[kOffWDepth + v];
-      combine_voxel_depth(*reinterpret_cast<const short *>(src + kOffSdf + v * 2), oldW, maxW, sdf, w);
-      dst[kOffWDepth + v] = (uint8_t)w;
-      *reinterpret_cast<short *>(dst + kOffSdf + v * 2) = sdf;
-    }
-    const uchar4 sc = *reinterpret_cast<const uchar4 *>(src + kOffClr + v * 4);  // (r, g, b, w_color)
-    if (sc.w != 0)
-      *reinterpret_cast<uchar4 *>(dst + kOffClr + v * 4) =
-          combine_voxel_colour(sc, *reinterpret_cast<const uchar4 *>(dst + kOffClr + v * 4), maxW);
   }
 }
 

@@ -3,7 +3,8 @@
 (gfx950 ISA of the <shared camera, plain weights> instantiation) priced with the issue rates MEASURED by
 tools/ubench/ubench_valu (profiles/r02a_ubench_valu*.log), against the cycles a task really takes.
 
-usage: python tools/isa_mix.py [kernel.s]      (default: compiles dynslam_amd/csrc/dsr_engine.hip to ISA)
+usage: python tools/isa_mix.py [kernel.s]      (default: compiles dynslam_amd/csrc/dsr_engine.hip, the one includer of k_integrate.h, to ISA;
+                                                the mesh kernels' unit is dsr_mesh.hip)
 The hot path is found structurally: basic blocks of the task loop, minus the blocks that contain the IEEE division
 sequence (camera-plane fallback, colour pass: rare) — the colour pass is added back with its measured frequency."""
 import os
