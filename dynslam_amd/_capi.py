@@ -645,3 +645,51 @@ def bind_esdf(lib, prefix):
     if ns.esdf_abi_version() != ESDF_ABI_VERSION:
         raise ImportError("esdf ABI version mismatch (include/dsr_esdf.h)")
     return ns
+
+
+# ---- include/dsr_query.h: distance, gradient and colour at arbitrary points.  A table of its own, like the ESDF's (the oracle has none).
+QUERY_ABI_VERSION = 1  # == DSR_QUERY_ABI_VERSION
+QUERY_NEAREST, QUERY_TRILINEAR = 0, 1  # DSR_QUERY_NEAREST / _TRILINEAR
+QUERY_HAS_DATA, QUERY_HAS_GRADIENT, QUERY_IN_BAND = 1, 2, 4  # DSR_QUERY_* flag bits
+QUERY_MAX_VOLUMES = 32  # DSR_QUERY_MAX_VOLUMES
+
+
+class QueryParams(C.Structure):  # struct dsr_query_params
+    _fields_ = [("query_to_world_m", C.c_float * 16), ("sampling", C.c_int32), ("min_w_depth", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+class QueryResult(C.Structure):  # struct dsr_query_result
+    _fields_ = [("points_with_data", C.c_int64), ("points_with_gradient", C.c_int64), ("reserved", C.c_int32 * 4)]
+
+
+assert C.sizeof(QueryParams) == 96 and C.sizeof(QueryResult) == 32
+
+# (engine, params, n, points, dist, grad, w_depth, rgba, flags, result)
+_QUERY_SINGLE = [_H, C.POINTER(QueryParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                 C.POINTER(QueryResult)]
+# (engines, params[k], k, n, points, dist, grad, volume, w_depth, rgba, flags, result)
+_QUERY_MULTI = [C.POINTER(_H), C.POINTER(QueryParams), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                C.c_void_p, C.c_void_p, C.POINTER(QueryResult)]
+QUERY_SIGNATURES = {
+    "query_abi_version": (C.c_int32, []),
+    "query_default_params": (None, [C.POINTER(QueryParams)]),
+    "query_points": (C.c_int, _QUERY_SINGLE),
+    "query_points_dev": (C.c_int, _QUERY_SINGLE),
+    "query_points_multi": (C.c_int, _QUERY_MULTI),
+    "query_points_multi_dev": (C.c_int, _QUERY_MULTI),
+}
+
+
+def bind_query(lib, prefix):
+    """The point-query entry points `prefix + name` in `lib`, or None when the library has none (the CPU oracle)."""
+    if not hasattr(lib, prefix + "query_points"):
+        return None
+    ns = SimpleNamespace()
+    for name, (res, args) in QUERY_SIGNATURES.items():
+        fn = getattr(lib, prefix + name)
+        fn.restype = res
+        fn.argtypes = args
+        setattr(ns, name, fn)
+    if ns.query_abi_version() != QUERY_ABI_VERSION:
+        raise ImportError("query ABI version mismatch (include/dsr_query.h)")
+    return ns

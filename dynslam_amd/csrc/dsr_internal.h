@@ -14,6 +14,8 @@
 //   dsr_mesh.hip      meshing (include/dsr.h, include/dsr_mesh.h): the soup mesh — resident, complete, coloured — and the indexed mesh;
 //                     their list step, plane pool and chunk loop, the read-backs, the OBJ / PLY writers, dsr_dump_merged_block
 //   dsr_esdf.hip      an exact Euclidean signed distance field from a dense grid (include/dsr_esdf.h): the checks, three launches
+//   dsr_query.hip     distance, gradient and colour of one or several volumes at arbitrary points (include/dsr_query.h): the checks,
+//                     the ordering of the engines' streams, the one launch
 // Every KERNEL header (k_*.h) is included by exactly ONE of them: __global__ kernels have external linkage.  Headers that hold only
 // inline device functions (dsr_device.h, dsr_math.h, dsr_sample.h) are shared: any unit may include them.
 #pragma once

@@ -1010,6 +1010,19 @@ class EngineCore:
         out.update(esdf_result_dict(res))
         return out
 
+    # ---- distance, gradient and colour at arbitrary points (include/dsr_query.h; builder-defined)
+    def query_points(self, points, pose=None, sampling="trilinear", min_w_depth=1, gradient=True, colour=False, torch_out=False):
+        """The volume at points (n, 3) float32 given in a frame that `pose` (4x4 row-major, rigid; None: identity) maps into the
+        engine's world — dsr_query_points.  Returns a dict: "dist" float32 (n,) signed distance in metres (mu where there is no
+        data), with gradient "grad" float32 (n, 3) — metres per metre in the frame of the points, away from the surface on the
+        observed side, zero where any of its samples lacks data —, "w_depth" uint8 (n,), with colour "rgba" uint8 (n, 4) = r, g, b,
+        w_color of the nearest voxel, "flags" uint8 (n,) (_capi.QUERY_HAS_DATA / _HAS_GRADIENT / _IN_BAND), and the counts
+        "points_with_data" / "points_with_gradient".  points: a numpy array, or a contiguous torch tensor on the engine's GPU
+        (ordered behind the current torch stream); with such a tensor, or torch_out, the planes are torch tensors on that GPU,
+        complete when the call returns.  Several volumes at once: dynslam_amd.query.query_world.  Reads only."""
+        from . import query
+        return query.run_query([(self, pose)], points, sampling, min_w_depth, gradient, colour, torch_out, multi=False)
+
     # ---- aligning another volume to this one (include/dsr_align.h, DESIGN.md §18; builder-defined)
     def _align_api(self):
         if not hasattr(self, "_aapi"):
@@ -1291,6 +1304,11 @@ class InfiniTamDriver:
         """ITMMainEngine::ExportEsdf (builder-defined, include/dsr_esdf.h): the volume's Euclidean signed distance field on a
         regular lattice — EngineCore.to_esdf's dict of planes and counts (INTEGRATION.md "distance fields")."""
         return self.core.to_esdf(shape, pitch, grid_to_world, **kwargs)
+
+    def QueryPoints(self, points, pose=None, **kwargs):
+        """ITMMainEngine::QueryPoints (builder-defined, include/dsr_query.h): signed distance, gradient, weight and colour of the
+        volume at arbitrary points — EngineCore.query_points's dict of planes and counts (INTEGRATION.md "collision check")."""
+        return self.core.query_points(points, pose, **kwargs)
 
     def ImportDense(self, sdf, w_depth=None, rgba=None, **kwargs):
         """ITMMainEngine::ImportDense (builder-defined, include/dsr_dense.h): a dense grid written into the volume —

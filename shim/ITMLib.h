@@ -31,6 +31,7 @@
 #include "../include/dsr_align.h"
 #include "../include/dsr_dense.h"
 #include "../include/dsr_esdf.h"
+#include "../include/dsr_query.h"
 
 // The tracker's entry points are referenced WEAKLY: a host linked against a library without them (the CPU oracle's orc_* build
 // of the reference's hosts) still links, and ITMTrackingController::Track then throws as it did before the tracker existed.
@@ -64,6 +65,10 @@ void dsr_dense_default_grid(dsr_dense_grid *g) __attribute__((weak));
 int dsr_esdf_export(dsr_engine *e, const dsr_dense_grid *grid, const dsr_esdf_params *params, float *dist, uint8_t *flags,
                     int32_t *d2_out, int32_t *d2_in, dsr_esdf_result *result) __attribute__((weak));
 void dsr_esdf_default_params(dsr_esdf_params *p) __attribute__((weak));
+// ... and the point queries' (include/dsr_query.h): QueryPoints throws on a library without them
+int dsr_query_points(dsr_engine *e, const dsr_query_params *params, int32_t n, const float *points_xyz, float *dist, float *grad_xyz,
+                     uint8_t *w_depth, uint8_t *rgba, uint8_t *flags, dsr_query_result *result) __attribute__((weak));
+void dsr_query_default_params(dsr_query_params *p) __attribute__((weak));
 // ... and the volume alignment's (include/dsr_align.h): AlignFrom throws on a library without it
 int dsr_align_volume(dsr_engine *dst, dsr_engine *src, const float init_src_to_dst_m[16], const dsr_align_params *params,
                      dsr_align_result *result, dsr_align_log_entry *log, int32_t log_capacity, int32_t *log_count) __attribute__((weak));
@@ -699,6 +704,23 @@ class ITMMainEngine {
     dsr_esdf_result res;
     memset(&res, 0, sizeof res);
     ITMLib::Engine::dsr_throw(dsr_esdf_export(engine_, &grid, &params, dist, flags, d2_out, d2_in, &res));
+    return res;
+  }
+  // BUILDER-DEFINED (include/dsr_query.h): signed distance, gradient, depth weight, colour and flags of the volume
+  // at n points (x, y, z interleaved) given in the frame params.query_to_world_m maps into the engine's world; any output may be
+  // null.  DefaultQueryParams gives the defaults to start from.  Reads only.
+  static dsr_query_params DefaultQueryParams() {
+    if (!dsr_query_default_params) throw std::runtime_error("this library has no point queries (include/dsr_query.h)");
+    dsr_query_params p;
+    dsr_query_default_params(&p);
+    return p;
+  }
+  dsr_query_result QueryPoints(const dsr_query_params &params, int32_t n, const float *points_xyz, float *dist, float *grad_xyz,
+                               uint8_t *w_depth, uint8_t *rgba, uint8_t *flags) {
+    if (!dsr_query_points) throw std::runtime_error("this library has no point queries (include/dsr_query.h)");
+    dsr_query_result res;
+    memset(&res, 0, sizeof res);
+    ITMLib::Engine::dsr_throw(dsr_query_points(engine_, &params, n, points_xyz, dist, grad_xyz, w_depth, rgba, flags, &res));
     return res;
   }
   dsr_dense_result ImportDense(const dsr_dense_grid &grid, const float *sdf, const uint8_t *w_depth, const uint8_t *rgba) {
