@@ -693,3 +693,48 @@ def bind_query(lib, prefix):
     if ns.query_abi_version() != QUERY_ABI_VERSION:
         raise ImportError("query ABI version mismatch (include/dsr_query.h)")
     return ns
+
+
+# ---- include/dsr_heightmap.h: a bird's-eye height map over a dense grid's columns.  A table of its own, like the queries' (the oracle has none).
+HEIGHTMAP_ABI_VERSION = 1  # == DSR_HEIGHTMAP_ABI_VERSION
+HEIGHTMAP_HAS_DATA, HEIGHTMAP_HAS_GROUND, HEIGHTMAP_HAS_CEILING, HEIGHTMAP_MULTI, HEIGHTMAP_OBSTACLE = 1, 2, 4, 8, 16  # DSR_HEIGHTMAP_* flag bits
+HEIGHTMAP_NONE = -1.0   # DSR_HEIGHTMAP_NONE
+HEIGHTMAP_MAX_NZ = 4096  # DSR_HEIGHTMAP_MAX_NZ
+
+
+class HeightmapParams(C.Structure):  # struct dsr_heightmap_params
+    _fields_ = [("band_lo", C.c_float), ("band_hi", C.c_float), ("reserved", C.c_int32 * 6)]
+
+
+class HeightmapResult(C.Structure):  # struct dsr_heightmap_result
+    _fields_ = [("samples_with_data", C.c_int64), ("columns_with_data", C.c_int64), ("columns_with_ground", C.c_int64),
+                ("columns_with_ceiling", C.c_int64), ("columns_multi", C.c_int64), ("columns_obstacle", C.c_int64),
+                ("reserved", C.c_int32 * 4)]
+
+
+assert C.sizeof(HeightmapParams) == 32 and C.sizeof(HeightmapResult) == 64
+
+# (engine, grid, params, ground, top, ceiling, rgba, flags, n_up, cost, result)
+_HEIGHTMAP_EXPORT = [_H, C.POINTER(DenseGrid), C.POINTER(HeightmapParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                     C.c_void_p, C.c_void_p, C.POINTER(HeightmapResult)]
+HEIGHTMAP_SIGNATURES = {
+    "heightmap_abi_version": (C.c_int32, []),
+    "heightmap_default_params": (None, [C.POINTER(HeightmapParams)]),
+    "heightmap_export": (C.c_int, _HEIGHTMAP_EXPORT),
+    "heightmap_export_dev": (C.c_int, _HEIGHTMAP_EXPORT),
+}
+
+
+def bind_heightmap(lib, prefix):
+    """The height-map entry points `prefix + name` in `lib`, or None when the library has none (the CPU oracle)."""
+    if not hasattr(lib, prefix + "heightmap_export"):
+        return None
+    ns = SimpleNamespace()
+    for name, (res, args) in HEIGHTMAP_SIGNATURES.items():
+        fn = getattr(lib, prefix + name)
+        fn.restype = res
+        fn.argtypes = args
+        setattr(ns, name, fn)
+    if ns.heightmap_abi_version() != HEIGHTMAP_ABI_VERSION:
+        raise ImportError("heightmap ABI version mismatch (include/dsr_heightmap.h)")
+    return ns

@@ -16,8 +16,9 @@
 //   dsr_esdf.hip      an exact Euclidean signed distance field from a dense grid (include/dsr_esdf.h): the checks, three launches
 //   dsr_query.hip     distance, gradient and colour of one or several volumes at arbitrary points (include/dsr_query.h): the checks,
 //                     the ordering of the engines' streams, the one launch
+//   dsr_heightmap.hip a bird's-eye height map of a volume over a dense grid's columns (include/dsr_heightmap.h): the checks, the one launch
 // Every KERNEL header (k_*.h) is included by exactly ONE of them: __global__ kernels have external linkage.  Headers that hold only
-// inline device functions (dsr_device.h, dsr_math.h, dsr_sample.h) are shared: any unit may include them.
+// inline device functions (dsr_device.h, dsr_math.h, dsr_sample.h, k_dense_sample.h) are shared: any unit may include them.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -39,6 +40,9 @@
 #include "../../include/dsr_track.h"
 
 using namespace dsr;
+
+struct dsr_dense_grid;           // include/dsr_dense.h
+namespace dsr { struct DenseP; } // k_dense_sample.h
 
 namespace dsr_internal {
 std::string &last_error();  // thread-local message behind dsr_last_error() (dsr_engine.hip)
@@ -374,6 +378,9 @@ int engine_render(dsr_engine *e, int type, const float pose_m[16], const float i
 // dsr_mesh.hip: release the soup mesh (meshTris, meshClr; what dsr_mesh_free does behind its entry check) — a snapshot load replaces
 // the state it was made from
 int mesh_release(dsr_engine *e);
+// dsr_merge.hip: every DSR_E_ARG of a dsr_dense_grid (include/dsr_dense.h) for engine e; fills the export's kernel parameters g and the
+// number of grid points n.  importFields: fill_w and import_mode are checked too.  Also the height maps' check (dsr_heightmap.hip)
+int dense_grid_check(dsr_engine *e, const dsr_dense_grid *grid, const char *what, bool importFields, dsr::DenseP &g, long long &n);
 // dsr_hostio.hip: is [p, p + bytes) inside a range the caller page-locked through dsr_pin_host_buffer?
 bool host_range_pinned(const void *p, size_t bytes);
 // dsr_profile.hip: div_short(x, b) == x / b for every x? (k_integrate.h; checked once per engine for its mu)

@@ -192,25 +192,21 @@ int dsr_merge_volume(dsr_engine *dst, dsr_engine *src, const float src_to_dst_m[
 // include/dsr_dense.h.  Export: ONE launch of k_dense_export over the grid's tiles.  Import: the candidate box as
 // keys (already in insert order), has-data, the merge's ordered insert, the pull; ONE host wait for the result words.
 
-namespace {
-
-struct DenseCall { DenseP g; long long n; };  // the checked arguments of one call: kernel parameters, grid points
-
-// every DSR_E_ARG of dsr_dense.h; fills c for the export (import_setup below completes it for the import)
-int dense_check(dsr_engine *e, const dsr_dense_grid *grid, const char *what, DenseCall &c) {
+// every DSR_E_ARG of dsr_dense.h's grid; fills g for the export and n with the grid points.  importFields: fill_w and import_mode are
+// checked too (the height maps, dsr_heightmap.hip, ignore them)
+int dsr_internal::dense_grid_check(dsr_engine *e, const dsr_dense_grid *grid, const char *what, bool importFields, DenseP &g, long long &n) {
   const std::string w(what);
   if (!e || !grid) return fail(DSR_E_ARG, w + ": null argument");
   if (e->s.use_swapping) return fail(DSR_E_ARG, w + ": engines with use_swapping are not supported");
   if (grid->nx < 1 || grid->ny < 1 || grid->nz < 1) return fail(DSR_E_ARG, w + ": a grid needs at least one point per axis");
-  c.n = (long long)grid->nx * grid->ny;
-  if (c.n > 2147483647ll || (c.n *= grid->nz) > 2147483647ll) return fail(DSR_E_ARG, w + ": more than 2^31 - 1 grid points");
+  n = (long long)grid->nx * grid->ny;
+  if (n > 2147483647ll || (n *= grid->nz) > 2147483647ll) return fail(DSR_E_ARG, w + ": more than 2^31 - 1 grid points");
   if (!std::isfinite(grid->pitch) || grid->pitch <= 0.0f) return fail(DSR_E_ARG, w + ": pitch must be finite and positive");
   if (std::isnan(grid->mu) || std::isinf(grid->mu)) return fail(DSR_E_ARG, w + ": mu is not finite");
-  if (grid->fill_w < 1 || grid->fill_w > 255) return fail(DSR_E_ARG, w + ": fill_w outside 1..255");
+  if (importFields && (grid->fill_w < 1 || grid->fill_w > 255)) return fail(DSR_E_ARG, w + ": fill_w outside 1..255");
   if (grid->sampling != DSR_DENSE_NEAREST && grid->sampling != DSR_DENSE_TRILINEAR) return fail(DSR_E_ARG, w + ": unknown sampling");
-  if (grid->import_mode != DSR_DENSE_REPLACE && grid->import_mode != DSR_DENSE_COMBINE) return fail(DSR_E_ARG, w + ": unknown import_mode");
+  if (importFields && grid->import_mode != DSR_DENSE_REPLACE && grid->import_mode != DSR_DENSE_COMBINE) return fail(DSR_E_ARG, w + ": unknown import_mode");
   if (!rigid_transform(grid->grid_to_world_m)) return fail(DSR_E_ARG, w + ": grid_to_world is not a rigid transform");
-  DenseP &g = c.g;
   g = DenseP{};
   const float vs = e->s.voxel_size, muGrid = grid->mu > 0.0f ? grid->mu : e->s.mu;
   memcpy(g.a.m, grid->grid_to_world_m, sizeof g.a.m);
@@ -225,6 +221,15 @@ int dense_check(dsr_engine *e, const dsr_dense_grid *grid, const char *what, Den
   g.maxW = e->s.max_w;
   g.buckets = e->noBuckets; g.mask = (uint32_t)(e->noBuckets - 1);
   return DSR_OK;
+}
+
+namespace {
+
+struct DenseCall { DenseP g; long long n; };  // the checked arguments of one call: kernel parameters, grid points
+
+// every DSR_E_ARG of dsr_dense.h; fills c for the export (import_setup below completes it for the import)
+int dense_check(dsr_engine *e, const dsr_dense_grid *grid, const char *what, DenseCall &c) {
+  return dsr_internal::dense_grid_check(e, grid, what, true, c.g, c.n);
 }
 
 bool misaligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }

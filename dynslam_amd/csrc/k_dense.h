@@ -8,42 +8,16 @@
 //   k_dense_candidates  the import's candidate blocks: a box of blocks, written as keys in the insert's order (no sort needed);
 //   k_dense_has_data    one wave per candidate: does any of its 512 voxels get data?  where is it in the table?
 //   k_dense_pull        one wave per block with data, 8 voxels per lane in the plane-wise layout.
-// dense_sample_volume / dense_sample_grid are the per-point definitions; tests/denseref/dense_ref.cpp restates them serially.
+// dense_sample_volume (k_dense_sample.h, shared with the height maps) / DenseGridSource::sample are the per-point definitions;
+// tests/denseref/dense_ref.cpp restates them serially.
 #pragma once
-#include "dsr_sample.h"
+#include "k_dense_sample.h"
 
 namespace dsr {
 
 constexpr int kDenseTileX = 16, kDenseTileY = 4, kDenseTileZ = 4;  // grid points per wave; 4 consecutive x per lane
 
-struct DenseP {
-  Mat4 a;                  // export: grid_to_world; import: its inverse
-  float scale, tx, ty, tz; // export: pitch / vs, t / vs; import: vs / pitch, t_inv / pitch (dsr_dense.h step 1 of either)
-  float ratio;             // export: mu / grid.mu; import: grid.mu / mu
-  int nx, ny, nz;
-  int trilinear, minW, combine, fillW, maxW;
-  int buckets; uint32_t mask;
-  int hiX, hiY, hiZ, cx, cy;  // import: the candidate box — its upper corner (blocks) and its extent along x and y
-};
-
 // ------------------------------------------------------------------ export
-
-struct DenseOut { bool valid; float sdf; int w; uint32_t clr; };
-
-// grid point (gx, gy, gz) sampled from the volume (dsr_dense.h export steps 1-3)
-__device__ __forceinline__ DenseOut dense_sample_volume(const DenseP &g, const VolumeP &vol, const BlockBox &box, const int *__restrict__ boxPtr,
-                                                        BlockCache &cache, bool wantClr, int gx, int gy, int gz) {
-  DenseOut r; r.valid = false; r.sdf = 1.0f; r.w = 0; r.clr = 0u;
-  const LatticeCell q = lattice_cell(lattice_pos(g.a, g.scale, g.tx, g.ty, g.tz, gx, gy, gz));
-  Corners c;
-  if (!gather_corners(vol, box, boxPtr, cache, q, g.trilinear ? GATHER_WEIGHTED : GATHER_NEAREST, g.minW, c)) return r;
-  const float sdfS = g.trilinear ? trilinear8(c.v, q.cx, q.cy, q.cz) : c.nearV;
-  r.sdf = (sdfS / 32767.0f) * g.ratio;
-  r.w = c.nearW;
-  r.valid = true;
-  if (wantClr && c.nearBlk) r.clr = *reinterpret_cast<const uint32_t *>(c.nearBlk + kOffClr + c.nearLin * 4);
-  return r;
-}
 
 // One wave per tile of 16 x 4 x 4 grid points; lane = 4 consecutive x of one row (x quad = lane & 3, y = (lane >> 2) & 3,
 // z = lane >> 4).  Four neighbouring lanes write one row of the tile: 64 contiguous bytes of the sdf and rgba planes, 16 of the

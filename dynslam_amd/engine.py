@@ -118,6 +118,11 @@ def _ptr(a):
 # the output planes of include/dsr_esdf.h in the order of its entry points, with their element types (numpy and torch share the names)
 ESDF_PLANES = {"dist": "float32", "flags": "uint8", "d2_out": "int32", "d2_in": "int32"}
 ESDF_RESULT_KEYS = ("points_with_data", "outside_sites", "inside_sites", "band_points", "far_points")
+# the output planes of include/dsr_heightmap.h in the order of its entry points: name -> (element type, trailing shape)
+HEIGHTMAP_PLANES = {"ground": ("float32", ()), "top": ("float32", ()), "ceiling": ("float32", ()), "rgba": ("uint8", (4,)),
+                    "flags": ("uint8", ()), "n_up": ("uint8", ()), "cost": ("float32", ())}
+HEIGHTMAP_COUNTS = ("samples_with_data", "columns_with_data", "columns_with_ground", "columns_with_ceiling", "columns_multi",
+                    "columns_obstacle")
 
 
 def _esdf_plane_names(planes):
@@ -1023,6 +1028,64 @@ class EngineCore:
         from . import query
         return query.run_query([(self, pose)], points, sampling, min_w_depth, gradient, colour, torch_out, multi=False)
 
+    # ---- a bird's-eye height map over a dense grid's columns (include/dsr_heightmap.h; builder-defined)
+    def _heightmap_api(self):
+        if not hasattr(self, "_hapi"):
+            self._hapi = _capi.bind_heightmap(self.api.lib, self.api.prefix)
+        if self._hapi is None:
+            raise DsrError(_capi.DSR_E_ARG, f"this backend ({self.api.prefix}*) has no include/dsr_heightmap.h entry points")
+        return self._hapi
+
+    def to_heightmap(self, shape, pitch, grid_to_world=None, mu=None, sampling="trilinear", min_w_depth=1, band=(0.2, 2.0),
+                     planes=HEIGHTMAP_PLANES, out=None, torch_out=False):
+        """The columns of the lattice of to_dense (shape = (nz, ny, nx), `pitch` metres, grid_to_world; grid z is "up" — for a
+        y-down world dynslam_amd.heightmap.up_is_minus_y) reduced to two-dimensional layers — dsr_heightmap_export.  Returns a dict
+        of the `planes` asked for, each (ny, nx): "ground" / "top" float32 metres along grid z of the lowest / highest crossing from
+        solid below to free above, "ceiling" float32 the lowest crossing from free to solid above the ground (_capi.HEIGHTMAP_NONE
+        where there is none), "rgba" uint8 (ny, nx, 4) the colour at the top crossing, "flags" uint8 (_capi.HEIGHTMAP_* bits),
+        "n_up" uint8 the number of upward crossings, "cost" float32 (-1 obstacle: solid between band[0] and band[1] metres above
+        the ground; 0.5 ground; 1 unknown — what dynslam_amd.heightmap.clearance_2d takes); plus the counts of
+        dsr_heightmap_result.  out: a dict of preallocated planes to write into — numpy arrays, or contiguous torch tensors on the
+        engine's GPU, which are written there directly (ordered behind the current torch stream, complete when the call returns);
+        torch_out: allocate such tensors.  Reads only."""
+        api = self._heightmap_api()
+        g = self._dense_grid(shape, pitch, grid_to_world, mu, sampling, min_w_depth)
+        p = _capi.HeightmapParams()
+        api.heightmap_default_params(C.byref(p))
+        p.band_lo, p.band_hi = float(band[0]), float(band[1])
+        names = [k for k in HEIGHTMAP_PLANES if k in planes] if out is None else [k for k in HEIGHTMAP_PLANES if k in out]
+        unknown = [k for k in (planes if out is None else out) if k not in HEIGHTMAP_PLANES]
+        if unknown:
+            raise DsrError(_capi.DSR_E_ARG, f"to_heightmap: unknown planes {unknown}")
+        shapes = {k: (g.ny, g.nx) + HEIGHTMAP_PLANES[k][1] for k in names}
+        on_gpu = torch_out or (out is not None and any(not isinstance(v, np.ndarray) and hasattr(v, "data_ptr") for v in out.values()))
+        res = _capi.HeightmapResult()
+        if on_gpu:
+            import torch
+            dev = self._torch_device()
+            if out is None:
+                out = {k: torch.empty(shapes[k], dtype=getattr(torch, HEIGHTMAP_PLANES[k][0]), device=dev) for k in names}
+            for k in names:
+                t = out[k]
+                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == getattr(torch, HEIGHTMAP_PLANES[k][0]) and
+                        tuple(t.shape) == shapes[k] and t.is_contiguous()):
+                    raise DsrError(_capi.DSR_E_ARG, f"to_heightmap: {k} must be a contiguous {HEIGHTMAP_PLANES[k][0]} tensor of shape {shapes[k]} on the engine's GPU")
+            self.wait_for_stream(torch.cuda.current_stream(dev).cuda_stream)  # the tensors' earlier users first
+            ptrs = [out[k].data_ptr() if k in names else None for k in HEIGHTMAP_PLANES]
+            self._check(api.heightmap_export_dev(self._h, C.byref(g), C.byref(p), *ptrs, C.byref(res)))
+        else:
+            if out is None:
+                out = {k: np.empty(shapes[k], HEIGHTMAP_PLANES[k][0]) for k in names}
+            for k in names:
+                a = out[k]
+                if not (isinstance(a, np.ndarray) and a.dtype == np.dtype(HEIGHTMAP_PLANES[k][0]) and a.shape == shapes[k] and a.flags.c_contiguous):
+                    raise DsrError(_capi.DSR_E_ARG, f"to_heightmap: {k} must be a contiguous {HEIGHTMAP_PLANES[k][0]} array of shape {shapes[k]}")
+            ptrs = [_ptr(out[k]) if k in names else None for k in HEIGHTMAP_PLANES]
+            self._check(api.heightmap_export(self._h, C.byref(g), C.byref(p), *ptrs, C.byref(res)))
+        result = {k: out[k] for k in names}
+        result.update({k: int(getattr(res, k)) for k in HEIGHTMAP_COUNTS})
+        return result
+
     # ---- aligning another volume to this one (include/dsr_align.h, DESIGN.md §18; builder-defined)
     def _align_api(self):
         if not hasattr(self, "_aapi"):
@@ -1309,6 +1372,11 @@ class InfiniTamDriver:
         """ITMMainEngine::QueryPoints (builder-defined, include/dsr_query.h): signed distance, gradient, weight and colour of the
         volume at arbitrary points — EngineCore.query_points's dict of planes and counts (INTEGRATION.md "collision check")."""
         return self.core.query_points(points, pose, **kwargs)
+
+    def ExportHeightMap(self, shape, pitch, grid_to_world=None, **kwargs):
+        """ITMMainEngine::ExportHeightMap (builder-defined, include/dsr_heightmap.h): ground, top, ceiling, orthophoto, flags and
+        cost per column of a regular lattice — EngineCore.to_heightmap's dict of planes and counts (INTEGRATION.md "height maps")."""
+        return self.core.to_heightmap(shape, pitch, grid_to_world, **kwargs)
 
     def ImportDense(self, sdf, w_depth=None, rgba=None, **kwargs):
         """ITMMainEngine::ImportDense (builder-defined, include/dsr_dense.h): a dense grid written into the volume —

@@ -32,6 +32,7 @@
 #include "../include/dsr_dense.h"
 #include "../include/dsr_esdf.h"
 #include "../include/dsr_query.h"
+#include "../include/dsr_heightmap.h"
 
 // The tracker's entry points are referenced WEAKLY: a host linked against a library without them (the CPU oracle's orc_* build
 // of the reference's hosts) still links, and ITMTrackingController::Track then throws as it did before the tracker existed.
@@ -69,6 +70,11 @@ void dsr_esdf_default_params(dsr_esdf_params *p) __attribute__((weak));
 int dsr_query_points(dsr_engine *e, const dsr_query_params *params, int32_t n, const float *points_xyz, float *dist, float *grad_xyz,
                      uint8_t *w_depth, uint8_t *rgba, uint8_t *flags, dsr_query_result *result) __attribute__((weak));
 void dsr_query_default_params(dsr_query_params *p) __attribute__((weak));
+// ... and the height maps' (include/dsr_heightmap.h): ExportHeightMap throws on a library without them
+int dsr_heightmap_export(dsr_engine *e, const dsr_dense_grid *grid, const dsr_heightmap_params *params, float *ground, float *top,
+                         float *ceiling, uint8_t *rgba, uint8_t *flags, uint8_t *n_up, float *cost, dsr_heightmap_result *result)
+    __attribute__((weak));
+void dsr_heightmap_default_params(dsr_heightmap_params *p) __attribute__((weak));
 // ... and the volume alignment's (include/dsr_align.h): AlignFrom throws on a library without it
 int dsr_align_volume(dsr_engine *dst, dsr_engine *src, const float init_src_to_dst_m[16], const dsr_align_params *params,
                      dsr_align_result *result, dsr_align_log_entry *log, int32_t log_capacity, int32_t *log_count) __attribute__((weak));
@@ -704,6 +710,23 @@ class ITMMainEngine {
     dsr_esdf_result res;
     memset(&res, 0, sizeof res);
     ITMLib::Engine::dsr_throw(dsr_esdf_export(engine_, &grid, &params, dist, flags, d2_out, d2_in, &res));
+    return res;
+  }
+  // BUILDER-DEFINED (include/dsr_heightmap.h): the columns of the lattice `grid` describes — its z axis is "up" —
+  // reduced to host planes of grid.nx * grid.ny cells (any of them may be null): ground, top and ceiling heights, the orthophoto,
+  // flags, the number of upward crossings and the cost layer.  DefaultHeightMapParams gives the defaults to start from.  Reads only.
+  static dsr_heightmap_params DefaultHeightMapParams() {
+    if (!dsr_heightmap_default_params) throw std::runtime_error("this library has no height maps (include/dsr_heightmap.h)");
+    dsr_heightmap_params p;
+    dsr_heightmap_default_params(&p);
+    return p;
+  }
+  dsr_heightmap_result ExportHeightMap(const dsr_dense_grid &grid, const dsr_heightmap_params &params, float *ground, float *top,
+                                       float *ceiling, uint8_t *rgba, uint8_t *flags, uint8_t *n_up, float *cost) {
+    if (!dsr_heightmap_export) throw std::runtime_error("this library has no height maps (include/dsr_heightmap.h)");
+    dsr_heightmap_result res;
+    memset(&res, 0, sizeof res);
+    ITMLib::Engine::dsr_throw(dsr_heightmap_export(engine_, &grid, &params, ground, top, ceiling, rgba, flags, n_up, cost, &res));
     return res;
   }
   // BUILDER-DEFINED (include/dsr_query.h): signed distance, gradient, depth weight, colour and flags of the volume
