@@ -738,3 +738,48 @@ def bind_heightmap(lib, prefix):
     if ns.heightmap_abi_version() != HEIGHTMAP_ABI_VERSION:
         raise ImportError("heightmap ABI version mismatch (include/dsr_heightmap.h)")
     return ns
+
+
+# ---- include/dsr_erase.h: erase and crop — a volume cleared by oriented boxes or by another volume's surface.  A table of its own (the oracle has none).
+ERASE_ABI_VERSION = 1  # == DSR_ERASE_ABI_VERSION
+ERASE_INSIDE, ERASE_OUTSIDE = 0, 1  # DSR_ERASE_*
+ERASE_MAX_BOXES = 32  # DSR_ERASE_MAX_BOXES
+
+
+class EraseBox(C.Structure):  # struct dsr_obox
+    _fields_ = [("box_to_world_m", C.c_float * 16), ("half_extent_m", C.c_float * 3), ("reserved", C.c_float)]
+
+
+class EraseParams(C.Structure):  # struct dsr_erase_params
+    _fields_ = [("mode", C.c_int32), ("free_blocks", C.c_int32), ("min_w_depth", C.c_int32), ("margin_m", C.c_float),
+                ("reserved", C.c_int32 * 4)]
+
+
+class EraseResult(C.Structure):  # struct dsr_erase_result
+    _fields_ = [("blocks_examined", C.c_int32), ("blocks_touched", C.c_int32), ("blocks_freed", C.c_int32), ("reserved0", C.c_int32),
+                ("voxels_in_region", C.c_int64), ("voxels_erased", C.c_int64), ("reserved", C.c_int32 * 4)]
+
+
+assert C.sizeof(EraseBox) == 80 and C.sizeof(EraseParams) == 32 and C.sizeof(EraseResult) == 48
+
+ERASE_SIGNATURES = {
+    "erase_abi_version": (C.c_int32, []),
+    "erase_default_params": (None, [C.POINTER(EraseParams)]),
+    "erase_boxes": (C.c_int, [_H, C.c_int, C.POINTER(EraseBox), C.POINTER(EraseParams), C.POINTER(EraseResult)]),
+    "erase_by_volume": (C.c_int, [_H, _H, C.POINTER(C.c_float), C.POINTER(EraseParams), C.POINTER(EraseResult)]),
+}
+
+
+def bind_erase(lib, prefix):
+    """The erase entry points `prefix + name` in `lib`, or None when the library has none (the CPU oracle)."""
+    if not hasattr(lib, prefix + "erase_boxes"):
+        return None
+    ns = SimpleNamespace()
+    for name, (res, args) in ERASE_SIGNATURES.items():
+        fn = getattr(lib, prefix + name)
+        fn.restype = res
+        fn.argtypes = args
+        setattr(ns, name, fn)
+    if ns.erase_abi_version() != ERASE_ABI_VERSION:
+        raise ImportError("erase ABI version mismatch (include/dsr_erase.h)")
+    return ns

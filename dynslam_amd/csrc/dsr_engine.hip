@@ -162,7 +162,7 @@ void free_all(dsr_engine *e) {
   dsr_internal::tracker_free(e);
   F(e->tileSums); F(e->integrateStats); F(e->allocList); F(e->allocWork); F(e->meshTris); F(e->meshClr); F(e->imesh.verts); F(e->imesh.normals); F(e->imesh.colours); F(e->imesh.indices); F(e->rgb); F(e->depth); F(e->depthTmp); F(e->rawDepth); F(e->pointsMap); F(e->normalsMap);
   F(e->freeDepth); F(e->aosScratch);
-  F(e->fifoPlanes); F(e->decayCand); F(e->decayFlags);
+  F(e->fifoPlanes); F(e->decayCand); F(e->decayFlags); F(e->eraseRes);
   if (e->maskHost) (void)hipHostFree(e->maskHost);
   for (auto ev : e->maskEvent) if (ev) (void)hipEventDestroy(ev);
   F(e->scene.swapState); F(e->scene.swapStored); F(e->swapStagingDev); F(e->swapIdsDev); F(e->swapFlagsDev);
@@ -514,6 +514,24 @@ void dsr_internal::engine_scan_counts(dsr_engine *e, const SceneP &sc, const uin
   LAUNCH(e, "scan_tiles", k_scan_tile_sums, dim3(1), dim3(1024), tileSums, tiles, sc, (int)SCAN_MESH, 0);
   LAUNCH(e, "mesh_scan", k_u32_tile_offsets, dim3(tiles), dim3(kTileThreads), counts, nPtr, (const int2 *)tileSums, offsets);
 }
+void dsr_internal::engine_free_flagged(dsr_engine *e, const int32_t *cand, const int32_t *nCandPtr) {
+  RenderStateDev &rs = e->live;
+  LAUNCH(e, "decay_count", k_flag_count, dim3(e->numTilesB), dim3(kTileThreads), (const uint8_t *)e->decayFlags, nCandPtr,
+         e->tileSums);
+  LAUNCH(e, "scan_tiles", k_scan_tile_sums, dim3(1), dim3(1024), e->tileSums, e->numTilesB, e->scene, (int)SCAN_DECAY, 0);
+  LAUNCH(e, "decay_commit", k_decay_commit, dim3(e->numTilesB), dim3(kTileThreads), e->scene, cand, nCandPtr,
+         (const uint8_t *)e->decayFlags, (const int2 *)e->tileSums, rs.visType);
+  // drop freed entries from the live visible list (ordered compaction into the alternate buffer)
+  LAUNCH(e, "decay_compact", k_live_keep_count, dim3(e->numTilesB), dim3(kTileThreads), (const int32_t *)rs.visibleIDs,
+         (const int32_t *)e->scene.ctr, (const uint8_t *)rs.visType, e->tileSums);
+  LAUNCH(e, "scan_tiles", k_scan_tile_sums, dim3(1), dim3(1024), e->tileSums, e->numTilesB, e->scene,
+         (int)SCAN_COMPACT_LIVE, e->noBlocks);
+  LAUNCH(e, "decay_compact", k_live_keep_write, dim3(e->numTilesB), dim3(kTileThreads), (const int32_t *)rs.visibleIDs,
+         (const int32_t *)e->scene.ctr, (const uint8_t *)rs.visType, (const int2 *)e->tileSums, rs.visibleIDsAlt,
+         (const int4 *)rs.visBlocks, rs.visBlocksAlt);
+  std::swap(rs.visibleIDs, rs.visibleIDsAlt);
+  std::swap(rs.visBlocks, rs.visBlocksAlt);
+}
 int dsr_internal::engine_ensure_fifo(dsr_engine *e, int slots) { return ensure_fifo(e, slots); }
 int dsr_internal::engine_add_host_slab(dsr_engine *e) { return add_host_slab(e); }
 int dsr_internal::engine_small_bit_words() { return kSmallBitWords; }
@@ -676,6 +694,7 @@ int dsr_engine_create(const dsr_settings *settings, const dsr_calib *calib, dsr_
   ALLOC(dmalloc(&e->freeDepth, (size_t)e->P));
   ALLOC(dmalloc(&e->decayFlags, (size_t)e->noBlocks));
   ALLOC(dmalloc(&e->decayCand, (size_t)e->noBlocks));
+  ALLOC(dmalloc(reinterpret_cast<unsigned long long **>(&e->eraseRes), 1024));  // (8 KiB: the slots of k_erase.h EraseRes)
   ALLOC(dmalloc(&e->allocList, (size_t)e->noBlocks));
   if (s.use_swapping) {
     ALLOC(dmalloc(&e->scene.swapState, (size_t)e->E));
@@ -979,21 +998,7 @@ int dsr_decay(dsr_engine *e, int max_weight, int min_age, int force_all_voxels) 
   const int zeroIsReset = (((-1.0f > muv) || (fabsf(-1.0f / muv) > 0.25f)) && e->s.max_w >= 1) ? 1 : 0;
   LAUNCH(e, "decay_blocks", k_decay_blocks, dim3(e->gridDecay), dim3(256), e->scene, cand, nCandPtr, max_weight,
          e->decayFlags, zeroIsReset);
-  LAUNCH(e, "decay_count", k_flag_count, dim3(e->numTilesB), dim3(kTileThreads), (const uint8_t *)e->decayFlags, nCandPtr,
-         e->tileSums);
-  LAUNCH(e, "scan_tiles", k_scan_tile_sums, dim3(1), dim3(1024), e->tileSums, e->numTilesB, e->scene, (int)SCAN_DECAY, 0);
-  LAUNCH(e, "decay_commit", k_decay_commit, dim3(e->numTilesB), dim3(kTileThreads), e->scene, cand, nCandPtr,
-         (const uint8_t *)e->decayFlags, (const int2 *)e->tileSums, rs.visType);
-  // drop freed entries from the live visible list (ordered compaction into the alternate buffer)
-  LAUNCH(e, "decay_compact", k_live_keep_count, dim3(e->numTilesB), dim3(kTileThreads), (const int32_t *)rs.visibleIDs,
-         (const int32_t *)e->scene.ctr, (const uint8_t *)rs.visType, e->tileSums);
-  LAUNCH(e, "scan_tiles", k_scan_tile_sums, dim3(1), dim3(1024), e->tileSums, e->numTilesB, e->scene,
-         (int)SCAN_COMPACT_LIVE, e->noBlocks);
-  LAUNCH(e, "decay_compact", k_live_keep_write, dim3(e->numTilesB), dim3(kTileThreads), (const int32_t *)rs.visibleIDs,
-         (const int32_t *)e->scene.ctr, (const uint8_t *)rs.visType, (const int2 *)e->tileSums, rs.visibleIDsAlt,
-         (const int4 *)rs.visBlocks, rs.visBlocksAlt);
-  std::swap(rs.visibleIDs, rs.visibleIDsAlt);
-  std::swap(rs.visBlocks, rs.visBlocksAlt);
+  engine_free_flagged(e, cand, nCandPtr);
   HIP_TRY(hipGetLastError());
   return DSR_OK;
 }

@@ -17,6 +17,8 @@
 //   dsr_query.hip     distance, gradient and colour of one or several volumes at arbitrary points (include/dsr_query.h): the checks,
 //                     the ordering of the engines' streams, the one launch
 //   dsr_heightmap.hip a bird's-eye height map of a volume over a dense grid's columns (include/dsr_heightmap.h): the checks, the one launch
+//   dsr_erase.hip     erase and crop: a volume cleared by oriented boxes or by another volume's surface (include/dsr_erase.h): the checks,
+//                     the candidates, the one launch of k_erase.h, then the voxel GC's own commit and compaction
 // Every KERNEL header (k_*.h) is included by exactly ONE of them: __global__ kernels have external linkage.  Headers that hold only
 // inline device functions (dsr_device.h, dsr_math.h, dsr_sample.h, k_dense_sample.h) are shared: any unit may include them.
 #pragma once
@@ -43,6 +45,7 @@ using namespace dsr;
 
 struct dsr_dense_grid;           // include/dsr_dense.h
 namespace dsr { struct DenseP; } // k_dense_sample.h
+namespace dsr { struct EraseRes; } // k_erase.h
 
 namespace dsr_internal {
 std::string &last_error();  // thread-local message behind dsr_last_error() (dsr_engine.hip)
@@ -256,6 +259,7 @@ struct dsr_engine {
   bool xEvent2System = false;        // ... created with a system-scope release (an instance on another GPU has waited for it)
   hipEvent_t orderEvent = nullptr;   // dsr_wait_for_stream / dsr_stream_wait_for_engine
   uint8_t *decayFlags = nullptr;
+  struct dsr::EraseRes *eraseRes = nullptr;  // the result records of the running dsr_erase_* call (dsr_erase.hip; 8 KiB), device
 
   // PAIRED RENDER (round 6; instance-sized volumes).  dsr_prepare's tracking render (k_raycast_box + k_icp_maps_box) is not queued
   // at once: it is DEFERRED until the next call on this engine.  When that call is the preview render (dsr_get_image_dev /
@@ -362,6 +366,10 @@ void engine_prof_resolve(dsr_engine *e);
 // view's list, a snapshot and the meshers (dsr_mesh.hip) all list through this
 void engine_list_entries(dsr_engine *e, const char *label, bool owning, const SceneP &sc, int2 *tileSums, int32_t *out, int capacity,
                          int lengthCtr = CTR_DECAY_NCAND);
+// ... the tail of a forced voxel GC pass, for dsr_decay and dsr_erase.hip: the candidates flagged in e->decayFlags are freed in candidate
+// order (k_flag_count, scan, k_decay_commit: tombstones, the block free list) and dropped from the live visible list and its stream
+// (k_live_keep_*), order kept
+void engine_free_flagged(dsr_engine *e, const int32_t *cand, const int32_t *nCandPtr);
 // ... for dsr_mesh.hip: exclusive offsets of the *nPtr (host's view of it: n) u32 counts, their total left in CTR_MESH_TOTAL of sc's
 // counters.  tileSums: div_up(n, kTile) elements
 void engine_scan_counts(dsr_engine *e, const SceneP &sc, const uint32_t *counts, const int32_t *nPtr, int n, int2 *tileSums,

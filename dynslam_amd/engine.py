@@ -868,6 +868,52 @@ class EngineCore:
             raise
         return out
 
+    # ---- erase and crop (include/dsr_erase.h; builder-defined)
+    def _erase_api(self):
+        if not hasattr(self, "_eapi"):
+            self._eapi = _capi.bind_erase(self.api.lib, self.api.prefix)
+        if self._eapi is None:
+            raise DsrError(_capi.DSR_E_ARG, f"this backend ({self.api.prefix}*) has no include/dsr_erase.h entry points")
+        return self._eapi
+
+    def _erase_params(self, mode, free_blocks, min_w_depth=1, margin=0.0):
+        modes = {"inside": _capi.ERASE_INSIDE, "outside": _capi.ERASE_OUTSIDE}
+        if mode not in modes:
+            raise ValueError(f"mode is 'inside' or 'outside', not {mode!r}")
+        prm = _capi.EraseParams()
+        self._erase_api().erase_default_params(C.byref(prm))
+        prm.mode, prm.free_blocks, prm.min_w_depth, prm.margin_m = modes[mode], int(bool(free_blocks)), int(min_w_depth), float(margin)
+        return prm
+
+    @staticmethod
+    def _erase_result(res):
+        return {k: int(getattr(res, k)) for k in ("blocks_examined", "blocks_touched", "blocks_freed", "voxels_in_region", "voxels_erased")}
+
+    def erase_boxes(self, boxes, mode="inside", free_blocks=True, want_result=True):
+        """Clear the voxels inside the union of `boxes` (mode "inside") or outside it ("outside": crop) — dsr_erase_boxes.  boxes: a
+        sequence of (box_to_world 4x4 row-major, half extents in metres), see dynslam_amd.erase.  Returns the counts as a dict, or
+        None with want_result=False: the call is then only queued on the engine's stream."""
+        boxes = list(boxes)
+        arr = (_capi.EraseBox * max(len(boxes), 1))()
+        for k, (m, h) in enumerate(boxes):
+            arr[k].box_to_world_m[:] = np.asarray(m, np.float32).reshape(4, 4).T.reshape(-1).tolist()
+            arr[k].half_extent_m[:] = np.asarray(h, np.float32).reshape(3).tolist()
+        prm = self._erase_params(mode, free_blocks)
+        res = _capi.EraseResult()
+        self._check(self._erase_api().erase_boxes(self._h, len(boxes), arr, C.byref(prm), C.byref(res) if want_result else None))
+        return self._erase_result(res) if want_result else None
+
+    def erase_by_volume(self, src, src_to_dst, margin=0.0, min_w_depth=1, mode="inside", free_blocks=True, want_result=True):
+        """Clear the voxels of this volume that lie on or behind the surface of engine `src`'s volume, plus `margin` metres in front
+        (mode "inside"), or all others ("outside") — dsr_erase_by_volume.  src_to_dst: 4x4 row-major, metres of src's world ->
+        metres of this engine's world.  Returns the counts as a dict, or None with want_result=False (queued)."""
+        m = np.ascontiguousarray(np.asarray(src_to_dst, np.float32).reshape(4, 4).T)
+        prm = self._erase_params(mode, free_blocks, min_w_depth, margin)
+        res = _capi.EraseResult()
+        self._check(self._erase_api().erase_by_volume(self._h, src._h, m.ctypes.data_as(C.POINTER(C.c_float)), C.byref(prm),
+                                                      C.byref(res) if want_result else None))
+        return self._erase_result(res) if want_result else None
+
     # ---- the volume as a dense grid and back (include/dsr_dense.h, DESIGN.md §19; builder-defined)
     def _dense_api(self):
         if not hasattr(self, "_dapi"):
@@ -1377,6 +1423,22 @@ class InfiniTamDriver:
         """ITMMainEngine::ExportHeightMap (builder-defined, include/dsr_heightmap.h): ground, top, ceiling, orthophoto, flags and
         cost per column of a regular lattice — EngineCore.to_heightmap's dict of planes and counts (INTEGRATION.md "height maps")."""
         return self.core.to_heightmap(shape, pitch, grid_to_world, **kwargs)
+
+    def EraseBoxes(self, boxes, mode="inside", **kwargs):
+        """ITMMainEngine::EraseBoxes (builder-defined, include/dsr_erase.h): the voxels inside the oriented boxes cleared, emptied
+        blocks handed back — EngineCore.erase_boxes's dict of counts (INTEGRATION.md "erase and crop")."""
+        return self.core.erase_boxes(boxes, mode=mode, **kwargs)
+
+    def EraseVolume(self, other, src_to_dst, margin=0.0, **kwargs):
+        """ITMMainEngine::EraseVolume (builder-defined, include/dsr_erase.h): what driver `other`'s volume occupies, at the rigid
+        transform src_to_dst (other's world -> this world), cut out of this one — the ghost of a vehicle that was fused into the map
+        before it became a tracked instance.  Returns EngineCore.erase_by_volume's dict of counts."""
+        return self.core.erase_by_volume(other.core, src_to_dst, margin=margin, **kwargs)
+
+    def CropToBox(self, box_to_world, half_extents, **kwargs):
+        """ITMMainEngine::CropToBox (builder-defined, include/dsr_erase.h): everything outside the oriented box cleared and its blocks
+        handed back — the sliding window of a map that follows the vehicle without host swapping."""
+        return self.core.erase_boxes([(box_to_world, half_extents)], mode="outside", **kwargs)
 
     def ImportDense(self, sdf, w_depth=None, rgba=None, **kwargs):
         """ITMMainEngine::ImportDense (builder-defined, include/dsr_dense.h): a dense grid written into the volume —

@@ -33,6 +33,7 @@
 #include "../include/dsr_esdf.h"
 #include "../include/dsr_query.h"
 #include "../include/dsr_heightmap.h"
+#include "../include/dsr_erase.h"
 
 // The tracker's entry points are referenced WEAKLY: a host linked against a library without them (the CPU oracle's orc_* build
 // of the reference's hosts) still links, and ITMTrackingController::Track then throws as it did before the tracker existed.
@@ -75,6 +76,12 @@ int dsr_heightmap_export(dsr_engine *e, const dsr_dense_grid *grid, const dsr_he
                          float *ceiling, uint8_t *rgba, uint8_t *flags, uint8_t *n_up, float *cost, dsr_heightmap_result *result)
     __attribute__((weak));
 void dsr_heightmap_default_params(dsr_heightmap_params *p) __attribute__((weak));
+// ... and erase and crop (include/dsr_erase.h): EraseBoxes / EraseVolume / CropToBox throw on a library without them
+int dsr_erase_boxes(dsr_engine *e, int n_boxes, const dsr_obox *boxes, const dsr_erase_params *params, dsr_erase_result *result)
+    __attribute__((weak));
+int dsr_erase_by_volume(dsr_engine *dst, dsr_engine *src, const float src_to_dst_m[16], const dsr_erase_params *params,
+                        dsr_erase_result *result) __attribute__((weak));
+void dsr_erase_default_params(dsr_erase_params *p) __attribute__((weak));
 // ... and the volume alignment's (include/dsr_align.h): AlignFrom throws on a library without it
 int dsr_align_volume(dsr_engine *dst, dsr_engine *src, const float init_src_to_dst_m[16], const dsr_align_params *params,
                      dsr_align_result *result, dsr_align_log_entry *log, int32_t log_capacity, int32_t *log_count) __attribute__((weak));
@@ -678,6 +685,37 @@ class ITMMainEngine {
     memset(&res, 0, sizeof res);
     ITMLib::Engine::dsr_throw(dsr_merge_volume(engine_, other.engine_, src_to_dst.m, nullptr, &res));
     return res;
+  }
+  // BUILDER-DEFINED (include/dsr_erase.h): the voxels inside the union of n oriented boxes cleared (EraseBoxes), the
+  // voxels on or behind the surface of `other`'s volume at src_to_dst, plus margin_m in front (EraseVolume: the ghost of a vehicle
+  // that was fused into the map before it became an instance), everything OUTSIDE one box (CropToBox: the sliding window of a map
+  // without host swapping).  Emptied blocks go back to the free list.  Raycast results are stale until the next Prepare.
+  static dsr_erase_params DefaultEraseParams() {
+    if (!dsr_erase_default_params) throw std::runtime_error("this library has no erase and crop (include/dsr_erase.h)");
+    dsr_erase_params p;
+    dsr_erase_default_params(&p);
+    return p;
+  }
+  dsr_erase_result EraseBoxes(int n, const dsr_obox *boxes, const dsr_erase_params *params = nullptr) {
+    if (!dsr_erase_boxes) throw std::runtime_error("this library has no erase and crop (include/dsr_erase.h)");
+    dsr_erase_result res;
+    memset(&res, 0, sizeof res);
+    ITMLib::Engine::dsr_throw(dsr_erase_boxes(engine_, n, boxes, params, &res));
+    return res;
+  }
+  dsr_erase_result EraseVolume(ITMMainEngine &other, const Matrix4f &src_to_dst, float margin_m = 0.0f) {
+    if (!dsr_erase_by_volume) throw std::runtime_error("this library has no erase and crop (include/dsr_erase.h)");
+    dsr_erase_params p = DefaultEraseParams();
+    p.margin_m = margin_m;
+    dsr_erase_result res;
+    memset(&res, 0, sizeof res);
+    ITMLib::Engine::dsr_throw(dsr_erase_by_volume(engine_, other.engine_, src_to_dst.m, &p, &res));
+    return res;
+  }
+  dsr_erase_result CropToBox(const dsr_obox &box) {
+    dsr_erase_params p = DefaultEraseParams();
+    p.mode = DSR_ERASE_OUTSIDE;
+    return EraseBoxes(1, &box, &p);
   }
   // BUILDER-DEFINED (include/dsr_dense.h): the volume sampled on the lattice `grid` describes into host planes of
   // grid.nx * grid.ny * grid.nz points (any of them may be null), and such planes written into the volume, allocating what it
