@@ -844,11 +844,11 @@ class EngineCore:
 
     # ---- folding another volume into this one (include/dsr_merge.h; builder-defined)
     def _merge_api(self):
-        if not hasattr(self, "_gapi"):
-            self._gapi = _capi.bind_merge(self.api.lib, self.api.prefix)
-        if self._gapi is None:
+        if not hasattr(self, "_mergeapi"):   # (an attribute of its own: `_gapi` is the voxel GC's)
+            self._mergeapi = _capi.bind_merge(self.api.lib, self.api.prefix)
+        if self._mergeapi is None:
             raise DsrError(_capi.DSR_E_ARG, f"this backend ({self.api.prefix}*) has no include/dsr_merge.h entry points")
-        return self._gapi
+        return self._mergeapi
 
     def merge_from(self, src, src_to_dst, min_w_depth=1, merge_colour=True):
         """Resample the volume of engine `src` into this one (dsr_merge_volume); src_to_dst: 4x4, metres of src's world -> metres
@@ -1026,11 +1026,11 @@ class EngineCore:
 
     # ---- the volume's Euclidean signed distance field on a dense grid (include/dsr_esdf.h; builder-defined)
     def _esdf_api(self):
-        if not hasattr(self, "_eapi"):
-            self._eapi = _capi.bind_esdf(self.api.lib, self.api.prefix)
-        if self._eapi is None:
+        if not hasattr(self, "_esdfapi"):   # (an attribute of its own: `_eapi` is the erase's)
+            self._esdfapi = _capi.bind_esdf(self.api.lib, self.api.prefix)
+        if self._esdfapi is None:
             raise DsrError(_capi.DSR_E_ARG, f"this backend ({self.api.prefix}*) has no include/dsr_esdf.h entry points")
-        return self._eapi
+        return self._esdfapi
 
     def to_esdf(self, shape, pitch, grid_to_world=None, *, max_distance=None, max_steps=32, mu=None, sampling="trilinear", min_w_depth=1,
                 keep_tsdf=True, planes=("dist", "flags"), torch_out=False):

@@ -12,12 +12,15 @@ def np_hash(pos, mask):
     return ((p[:, 0] * np.uint32(73856093)) ^ (p[:, 1] * np.uint32(19349669)) ^ (p[:, 2] * np.uint32(83492791))) & np.uint32(mask)
 
 
-def check_structure(e, n_blocks, n_buckets):
+def check_structure(e, n_blocks, n_buckets, blocks_given_up=False):
+    """blocks_given_up: a frame ran out of excess entries since the last reset and gave up the blocks it had popped for them (as
+    upstream does), so more blocks may be popped than entries hold; everything else holds as always"""
     st = e.get_stats()
     ht = e.dump_hash_table()
     used = np.nonzero(ht["ptr"] >= 0)[0]
     # free-list accounting (InfiniTamDriver.h:241-244)
-    assert n_blocks - 1 - st.last_free_block_id == len(used)
+    popped = n_blocks - 1 - st.last_free_block_id
+    assert popped >= len(used) if blocks_given_up else popped == len(used)
     # block pointers unique, disjoint from the live free list
     ptrs = ht["ptr"][used]
     assert len(np.unique(ptrs)) == len(ptrs)

@@ -2195,4 +2195,49 @@ int orc_set_threads(dsr_engine *h, int n) {
   return DSR_OK;
 }
 
+/* oracle-only: take on a scene state that an edit call (merge, dense import, erase: include/dsr_merge.h, dsr_dense.h,
+ * dsr_erase.h) left, computed by the call's serial restatement under tests/.  The oracle has no edit calls of its own; with this
+ * hook it follows an engine through them and goes on fusing, decaying and rendering from the edited state.
+ *  - overwritten: hash table, voxel blocks, both allocation lists with their heads, the live visible list with its count and its
+ *    visible types, decayedBlockCount;
+ *  - what the edit calls do beside: the free-view state is dropped.  The free-view visible types are cleared for every entry that
+ *    was freed or newly taken.  That is more than the GPU clears: there only k_merge_apply clears them, for the entries it takes,
+ *    and the free path (engine_free_flagged -> k_decay_commit) is handed the live types alone.  The difference cannot be seen: the
+ *    oracle's free-view render lists its visible blocks from the table alone (find_visible_blocks) and nothing reads these types;
+ *  - untouched: view, pose, the GC's ring of visible lists (its lists may name entries that were freed: the GC skips an entry
+ *    without a block), the frame counter, the live raycast buffers, the ICP maps, the sticky status. */
+int orc_set_scene_state(dsr_engine *h, const dsr_hash_entry *table, int32_t n_entries, const dsr_voxel *voxels, int32_t n_blocks,
+                        const int32_t *voxel_alloc_list, int32_t n_voxel_alloc, int32_t last_free_block_id,
+                        const int32_t *excess_alloc_list, int32_t n_excess_alloc, int32_t last_free_excess_list_id,
+                        const int32_t *visible_ids, int32_t n_visible, const uint8_t *visible_types, int32_t n_visible_types,
+                        int64_t decayed_block_count) {
+  if (!h || !table || !voxels || !voxel_alloc_list || !excess_alloc_list || !visible_types || (n_visible > 0 && !visible_ids))
+    return fail(DSR_E_ARG, "set_scene_state: null argument");
+  if (!E.swapStates.empty() || E.s.use_swapping) return fail(DSR_E_ARG, "set_scene_state: engines with use_swapping are not supported");
+  if (n_entries != E.noTotalEntries || n_blocks != E.noBlocks || n_voxel_alloc != E.noBlocks || n_excess_alloc != E.noExcess ||
+      n_visible_types != E.noTotalEntries)
+    return fail(DSR_E_ARG, "set_scene_state: an array has the wrong size");
+  if (last_free_block_id < -1 || last_free_block_id >= E.noBlocks || last_free_excess_list_id < -1 ||
+      last_free_excess_list_id >= E.noExcess || n_visible < 0 || n_visible > E.noBlocks || decayed_block_count < 0)
+    return fail(DSR_E_ARG, "set_scene_state: a head or a count is out of range");
+  for (int i = 0; i < n_visible; i++)
+    if (visible_ids[i] < 0 || visible_ids[i] >= E.noTotalEntries) return fail(DSR_E_ARG, "set_scene_state: a visible id is out of range");
+  for (int t = 0; t < n_entries; t++)
+    if (table[t].ptr >= E.noBlocks) return fail(DSR_E_ARG, "set_scene_state: an entry's block is out of range");
+  for (int t = 0; t < n_entries; t++)
+    if ((E.hashTable[t].ptr >= 0) != (table[t].ptr >= 0)) E.freeview.entriesVisibleType[t] = 0;
+  memcpy(E.hashTable.data(), table, (size_t)n_entries * sizeof(dsr_hash_entry));
+  memcpy(E.voxels.data(), voxels, (size_t)n_blocks * DSR_BLOCK_SIZE3 * sizeof(dsr_voxel));
+  memcpy(E.voxelAllocationList.data(), voxel_alloc_list, (size_t)n_voxel_alloc * 4);
+  memcpy(E.excessAllocationList.data(), excess_alloc_list, (size_t)n_excess_alloc * 4);
+  E.lastFreeBlockId = last_free_block_id;
+  E.lastFreeExcessListId = last_free_excess_list_id;
+  if (n_visible) memcpy(E.live.visibleEntryIDs.data(), visible_ids, (size_t)n_visible * 4);
+  E.live.noVisibleBlocks = n_visible;
+  memcpy(E.live.entriesVisibleType.data(), visible_types, (size_t)n_entries);
+  E.decayedBlockCount = decayed_block_count;
+  E.freeviewValid = false;
+  return DSR_OK;
+}
+
 } /* extern "C" */

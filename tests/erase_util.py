@@ -37,6 +37,17 @@ BOXES_3 = [BOX_A, BOX_R, BOX_S]
 CROP = (mu.rigid(0.0, 0.1, (0.2, 1.4, 9.0)), np.array([3.0, 1.0, 2.5], F))
 MARGIN_VOXEL = float(F(mu.COARSE["voxel_size"]))
 
+# The tombstoned dst of the ordered-insert tests (tests/test_merge_cpu.py, test_dense_cpu.py, test_gpu_fuzz_edit.py): COARSE fused
+# from mu.DST_FRAMES (512 blocks, two per bucket), TOMB_BOXES erased, then a forced GC pass at weight 1 — 88 blocks stay, 424
+# entries are tombstones, 256 of them inside chains.  "excess": 128 excess entries are left where the merge of FINE appends 189;
+# "blocks": 512 blocks are free where it inserts 518.  The CPU tests assert, from the tables, what the numbers were chosen for.
+TOMB_BOXES = [BOX_A, BOX_R]
+TOMB_DECAY = (1, 0, True)
+TOMB_KW = dict(plain=mu.COARSE, excess=dict(mu.COARSE, excess_list_size=0x180), blocks=dict(mu.COARSE, sdf_local_block_num=600))
+# the grid of the import into those states: coarser than dst, every point with data (no weight plane), so that it needs more
+# blocks and more excess entries than "blocks" and "excess" have
+TOMB_GRID = dict(shape=(40, 32, 24), pitch=0.1)
+
 _lib = None
 
 
@@ -104,6 +115,39 @@ def oracle_state(kw, frames):
         return state(o)
     finally:
         o.close()
+
+
+def tombstone_oracle(kw, frames=mu.DST_FRAMES, boxes=None, decay=TOMB_DECAY):
+    """-> (oracle engine, its state): fused from `frames`, `boxes` erased (the restatement, taken on through the oracle's
+    set_scene_state), then the GC pass `decay`.  The caller closes the engine."""
+    from oracle.oracle import OracleEngine, oracle_settings
+    sc = mu.scene()
+    o = OracleEngine(oracle_settings(**kw), mu.calib(sc))
+    mu.fuse(o, sc, frames, prepare=False)
+    status, after, _ = run_ref(state(o), kw, boxes=TOMB_BOXES if boxes is None else boxes)
+    assert status == 0
+    o.set_scene_state(after)
+    o.decay(*decay)
+    return o, state(o)
+
+
+def tombstone_gpu(e, frames=mu.DST_FRAMES, boxes=None, decay=TOMB_DECAY):
+    """the same calls on a HIP engine -> its state"""
+    mu.fuse(e, mu.scene(), frames, prepare=False)
+    e.erase_boxes(TOMB_BOXES if boxes is None else boxes)
+    e.decay(*decay)
+    return state(e)
+
+
+def after_insert(before, after):
+    """The complete state (as state() captures it) after a merge or an import whose restatement returned `after` from `before`:
+    new entries get visible type 0 (k_merge_apply); the visible list and the counters stay."""
+    out = dict(before)
+    out.update(after)
+    vt = np.ascontiguousarray(before["vis_types"], np.uint8).copy()
+    vt[(before["table"]["ptr"] < 0) & (after["table"]["ptr"] >= 0)] = 0
+    out["vis_types"] = vt
+    return out
 
 
 def assert_state_equal(a, b, what=""):

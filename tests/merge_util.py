@@ -136,3 +136,102 @@ def calib(sc):
 RIGID = rigid(0.05, -0.08, (0.013, -0.021, 0.017))
 SRC_FRAMES = (0, 1, 2)
 DST_FRAMES = (2, 4)
+
+
+# ---- a second, naive statement of include/dsr_merge.h steps 3 and 4 (the ordered insert the merge and the dense import share), in
+# plain Python over a copy of the table: tests/test_merge_cpu.py and tests/test_dense_cpu.py pin the restatements by it
+
+def bucket_of(pos, buckets):
+    """the table's hash of block positions pos [n, 3] -> uint32 [n]"""
+    p = np.asarray(pos).astype(np.int64).astype(np.uint32)   # (two's complement, as the engine's (uint32_t) of an int)
+    return ((p[:, 0] * np.uint32(73856093)) ^ (p[:, 1] * np.uint32(19349669)) ^ (p[:, 2] * np.uint32(83492791))) & np.uint32(buckets - 1)
+
+
+def naive_ordered_insert(st, kw, positions):
+    """Insert the block positions [(x, y, z)] that the table of state `st` lacks, one after the other -> (table, lfb, lfe, log);
+    log: per candidate in insert order (position, what, entry) with what in 'in_place', 'append', 'drop_block', 'drop_excess'."""
+    nb = kw["hash_bucket_num"]
+    table = st["table"].copy()
+    val, exl, lfb, lfe = st["val"], st["exl"], int(st["lfb"]), int(st["lfe"])
+    positions = [tuple(int(v) for v in p) for p in positions]
+    bucket = bucket_of(np.array(positions, np.int64).reshape(-1, 3), nb).tolist()
+    packed = [(x + 32768) | ((y + 32768) << 16) | ((z + 32768) << 32) for x, y, z in positions]
+    log = []
+    for k in sorted(range(len(positions)), key=lambda k: (bucket[k], -packed[k])):
+        e, target = bucket[k], -1
+        while True:
+            if table["ptr"][e] < -1:
+                target = e
+                break
+            if table["offset"][e] < 1:
+                break
+            e = nb + int(table["offset"][e]) - 1
+        if lfb < 0:
+            log.append((positions[k], "drop_block", -1))
+            continue
+        if target < 0 and lfe < 0:
+            log.append((positions[k], "drop_excess", -1))
+            continue
+        ptr = int(val[lfb])
+        lfb -= 1
+        if target >= 0:
+            log.append((positions[k], "in_place", target))
+        else:
+            target = nb + int(exl[lfe])
+            lfe -= 1
+            table["offset"][e] = target - nb + 1
+            table["offset"][target] = 0
+            log.append((positions[k], "append", target))
+        table["pos"][target] = positions[k]
+        table["ptr"][target] = ptr
+    return table, lfb, lfe, log
+
+
+def insert_corners(before, after, kw):
+    """What an ordered insert did, read off the tables before and after it -> dict of counts: entries taken in place, in place on an
+    entry of the excess part (a tombstone inside a chain), appended; buckets that took two or more in-place inserts; buckets that
+    took an in-place insert and an append."""
+    nb = kw["hash_bucket_num"]
+    tb, ta = before["table"], after["table"]
+    idx = np.arange(len(tb))
+    linked = np.zeros(len(tb), bool)
+    off = tb["offset"][tb["offset"] >= 1]
+    linked[nb + off - 1] = True
+    taken = (tb["ptr"] < -1) & (ta["ptr"] >= 0)
+    in_place = taken & ((idx < nb) | linked)
+    append = taken & ~in_place
+    b = bucket_of(ta["pos"], nb).astype(np.int64)
+    n_in = np.bincount(b[in_place], minlength=nb)
+    n_app = np.bincount(b[append], minlength=nb)
+    return dict(in_place=int(in_place.sum()), in_place_excess=int((in_place & (idx >= nb)).sum()), append=int(append.sum()),
+                buckets_two_in_place=int((n_in >= 2).sum()), buckets_in_place_and_append=int(((n_in >= 1) & (n_app >= 1)).sum()))
+
+
+def new_positions(before, after):
+    """the block positions a call added to the table"""
+    tb, ta = before["table"], after["table"]
+    return ta["pos"][(tb["ptr"] < 0) & (ta["ptr"] >= 0)].tolist()
+
+
+def check_insert_against_naive(before, kw, run, positions, name):
+    """Shared by tests/test_merge_cpu.py and tests/test_dense_cpu.py.  run(state) -> (status, after, result): a restatement's call on `state`; positions: the
+    blocks with data that the table lacks — what the same call adds to the "plain" state, where neither list runs out (which blocks
+    hold data depends on neither list).  The naive statement inserts them into `before`; table, both lists and both heads must equal
+    the restatement's.  -> (corners read off the tables, the naive log's drops per list)"""
+    present = set(map(tuple, before["table"]["pos"][before["table"]["ptr"] >= 0].tolist()))
+    assert positions and not present & set(map(tuple, positions))
+    status, after, res = run(before)
+    table, lfb, lfe, log = naive_ordered_insert(before, kw, positions)
+    what = [w for _, w, _ in log]
+    drops = dict(block=what.count("drop_block"), excess=what.count("drop_excess"))
+    assert np.array_equal(after["table"], table), f"{name}: table differs in {(after['table'] != table).sum()} entries"
+    assert (after["lfb"], after["lfe"]) == (lfb, lfe), name
+    assert np.array_equal(after["val"], before["val"]) and np.array_equal(after["exl"], before["exl"]), f"{name}: the lists only lose their tops"
+    assert res["blocks_allocated"] == what.count("in_place") + what.count("append") and res["blocks_dropped"] == sum(drops.values())
+    assert status == (3 if res["blocks_dropped"] else 0)   # DSR_E_OUT_OF_BLOCKS
+    corners = insert_corners(before, after, kw)
+    assert corners["in_place"] == what.count("in_place") and corners["append"] == what.count("append")
+    # the inputs reach the corners (conditions on the reference, read off the before-table): a tombstone inside a chain taken in
+    # place, two in-place inserts in one bucket, an in-place insert and an append in one bucket
+    assert corners["in_place_excess"] >= 1 and corners["buckets_two_in_place"] >= 1 and corners["buckets_in_place_and_append"] >= 1, (name, corners)
+    return corners, drops

@@ -356,3 +356,31 @@ def test_reference_runs_clean_under_sanitizers(tmp_path):
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "ok" in out.stdout
+
+
+# ---------------------------------------------------------------- the import's ordered insert into a table with tombstones
+
+@pytest.mark.parametrize("name", ["plain", "excess", "blocks"])
+def test_import_into_tombstones_equals_the_naive_insert(volumes, name):
+    """dsr_merge.h steps 3 and 4 — the insert the import shares with the merge — by the naive statement of tests/merge_util.py, on
+    the tombstoned dst states of tests/erase_util.py; the grid has data at every point, so that "excess" and "blocks" run out."""
+    from tests import erase_util as eu
+    kw = eu.TOMB_KW[name]
+    o, before = eu.tombstone_oracle(kw)
+    o.close()
+    src = volumes["fine"]
+    shape, pitch = eu.TOMB_GRID["shape"], eu.TOMB_GRID["pitch"]
+    T = du.place_rigid(src, mu.FINE, shape, pitch)
+    planes, _ = du.ref_export(src, mu.FINE, du.grid_spec(shape, pitch, T), planes=("sdf",))
+    g = du.grid_spec(shape, pitch, T, mu=mu.FINE["mu"], mode="combine", fill_w=3)
+    o, plain = eu.tombstone_oracle(eu.TOMB_KW["plain"])
+    o.close()
+    status, after, res = du.ref_import(plain, eu.TOMB_KW["plain"], g, planes["sdf"])
+    assert status == 0 and res["blocks_dropped"] == 0
+    corners, drops = mu.check_insert_against_naive(before, kw, lambda st: du.ref_import(st, kw, g, planes["sdf"]), mu.new_positions(plain, after), name)
+    if name == "plain":
+        assert drops == dict(block=0, excess=0)
+    elif name == "excess":
+        assert drops["excess"] >= 1 and drops["block"] == 0
+    else:
+        assert drops["block"] >= 1

@@ -229,3 +229,37 @@ def test_identity_merge_into_an_empty_volume(volumes):
         assert (a["sdf"][~has] == 32767).all()
         assert np.array_equal(a["w_color"][has], s["w_color"][has]), b
         assert (np.abs(a["clr"][has].astype(int) - s["clr"][has].astype(int)) <= 1).all(), b
+
+
+# ---------------------------------------------------------------- 3. the ordered insert into a table with tombstones
+
+@pytest.fixture(scope="module")
+def tombstoned():
+    from tests import erase_util as eu
+    out = {}
+    for name, kw in eu.TOMB_KW.items():
+        o, st = eu.tombstone_oracle(kw)
+        o.close()
+        out[name] = st
+    out["src"] = eu.oracle_state(mu.FINE, mu.SRC_FRAMES)
+    status, after, res = mu.run_ref(out["plain"], eu.TOMB_KW["plain"], out["src"], mu.FINE, mu.RIGID)
+    assert status == 0 and res["blocks_dropped"] == 0
+    out["positions"] = mu.new_positions(out["plain"], after)
+    assert len(out["positions"]) == res["blocks_allocated"]
+    return out
+
+
+@pytest.mark.parametrize("name", ["plain", "excess", "blocks"])
+def test_ordered_insert_into_tombstones_equals_the_naive_statement(tombstoned, name):
+    from tests import erase_util as eu
+    kw, before = eu.TOMB_KW[name], tombstoned[name]
+    t = before["table"]
+    assert ((t["ptr"] < -1) & (np.arange(len(t)) >= kw["hash_bucket_num"]) & (t["pos"] != 0).any(axis=1)).sum() > 0, "tombstones inside chains"
+    corners, drops = mu.check_insert_against_naive(before, kw, lambda st: mu.run_ref(st, kw, tombstoned["src"], mu.FINE, mu.RIGID),
+                                                tombstoned["positions"], name)
+    if name == "plain":
+        assert drops == dict(block=0, excess=0)
+    elif name == "excess":
+        assert drops["excess"] >= 1 and drops["block"] == 0
+    else:
+        assert drops["block"] >= 1
