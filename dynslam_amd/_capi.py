@@ -783,3 +783,61 @@ def bind_erase(lib, prefix):
     if ns.erase_abi_version() != ERASE_ABI_VERSION:
         raise ImportError("erase ABI version mismatch (include/dsr_erase.h)")
     return ns
+
+
+# ---- include/dsr_components.h: connected components of a dense grid, erase by a per-point mask, despeckle.  A table of its own (the oracle has none).
+COMPONENTS_ABI_VERSION = 1  # == DSR_COMPONENTS_ABI_VERSION
+COMP_BORDER, COMP_SMALL = 1, 2  # DSR_COMP_* flag bits
+
+
+class CompParams(C.Structure):  # struct dsr_comp_params
+    _fields_ = [("connectivity", C.c_int32), ("threshold", C.c_float), ("min_w_depth", C.c_int32), ("min_points", C.c_int32),
+                ("keep_border", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class Component(C.Structure):  # struct dsr_component
+    _fields_ = [("root", C.c_int32), ("points", C.c_int32), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("flags", C.c_int32),
+                ("reserved", C.c_int32), ("sum", C.c_int64 * 3)]
+
+
+class CompResult(C.Structure):  # struct dsr_comp_result
+    _fields_ = [("occupied_points", C.c_int64), ("small_points", C.c_int64), ("components", C.c_int32), ("components_written", C.c_int32),
+                ("small_components", C.c_int32), ("largest_points", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+assert C.sizeof(CompParams) == 32 and C.sizeof(Component) == 64 and C.sizeof(CompResult) == 48
+
+# (device, stream, nx, ny, nz, sdf, w_depth, occ, params, labels, table, capacity, mask, result)
+_COMP_PLANES = [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CompParams),
+                C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(CompResult)]
+# (engine, grid, params, labels, table, capacity, mask, result)
+_COMP_EXPORT = [_H, C.POINTER(DenseGrid), C.POINTER(CompParams), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(CompResult)]
+_ERASE_MASK = [_H, C.POINTER(DenseGrid), C.c_void_p, C.POINTER(EraseParams), C.POINTER(EraseResult)]
+COMPONENTS_SIGNATURES = {
+    "components_abi_version": (C.c_int32, []),
+    "components_default_params": (None, [C.POINTER(CompParams)]),
+    "components_from_planes_dev": (C.c_int, _COMP_PLANES),
+    "components_from_planes": (C.c_int, _COMP_PLANES),
+    "components_export": (C.c_int, _COMP_EXPORT),
+    "components_export_dev": (C.c_int, _COMP_EXPORT),
+    "erase_by_mask": (C.c_int, _ERASE_MASK),
+    "erase_by_mask_dev": (C.c_int, _ERASE_MASK),
+    "despeckle": (C.c_int, [_H, C.POINTER(DenseGrid), C.POINTER(CompParams), C.POINTER(EraseParams), C.POINTER(CompResult),
+                            C.POINTER(EraseResult)]),
+}
+
+
+def bind_components(lib, prefix):
+    """The entry points of include/dsr_components.h `prefix + name` in `lib`, or None when the library has none (an older library, the
+    CPU oracle)."""
+    if not hasattr(lib, prefix + "components_export"):
+        return None
+    ns = SimpleNamespace()
+    for name, (res, args) in COMPONENTS_SIGNATURES.items():
+        fn = getattr(lib, prefix + name)
+        fn.restype = res
+        fn.argtypes = args
+        setattr(ns, name, fn)
+    if ns.components_abi_version() != COMPONENTS_ABI_VERSION:
+        raise ImportError("components ABI version mismatch (include/dsr_components.h)")
+    return ns

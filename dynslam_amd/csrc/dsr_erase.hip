@@ -12,6 +12,7 @@ using namespace dsr_internal;
 #include "dsr_math.h"
 #include "k_erase.h"
 #include "../../include/dsr_erase.h"
+#include "../../include/dsr_components.h"  // dsr_erase_by_mask: the third region predicate
 
 static_assert(DSR_ERASE_MAX_BOXES == kEraseMaxBoxes, "dsr_erase.h and k_erase.h disagree");
 static_assert(sizeof(EraseRes) == 32 && kEraseResSlots * kEraseResStride * sizeof(EraseRes) == 8192, "dsr_engine_create allocates 8 KiB");
@@ -136,4 +137,56 @@ int dsr_erase_by_volume(dsr_engine *dst, dsr_engine *src, const float src_to_dst
   });
 }
 
+// ---- include/dsr_components.h B: the region given by a per-point mask on a dense grid
+
+int dsr_erase_by_mask_dev(dsr_engine *e, const dsr_dense_grid *grid, const uint8_t *mask_dev, const dsr_erase_params *params,
+                          dsr_erase_result *result) {
+  if (int st = erase_mask_check(e, grid, mask_dev, params)) return st;
+  dsr_erase_params prm;
+  if (int st = erase_params(params, "erase by mask", prm)) return st;
+  EraseMaskP m{};
+  float inv[16];
+  if (!dsr_math::m4_inv(grid->grid_to_world_m, inv)) return fail(DSR_E_ARG, "erase by mask: singular grid_to_world");
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 4; ++j) m.a[4 * i + j] = inv[4 * j + i];
+  m.vs = e->s.voxel_size;
+  m.pitch = grid->pitch;
+  m.nx = grid->nx; m.ny = grid->ny; m.nz = grid->nz;
+  m.mask = mask_dev;
+  CHECK_E(e);
+  return erase_run(e, result, [&](int launchGrid, const int32_t *cand, const int32_t *nCandPtr) {
+    LAUNCH(e, "erase_blocks", k_erase_blocks<EraseMask>, dim3(launchGrid), dim3(256), e->scene, m, e->scene, cand, nCandPtr,
+           (int)(prm.mode == DSR_ERASE_OUTSIDE), (int)(prm.free_blocks != 0), e->decayFlags, e->freeview.visType, e->eraseRes);
+  });
+}
+
+int dsr_erase_by_mask(dsr_engine *e, const dsr_dense_grid *grid, const uint8_t *mask, const dsr_erase_params *params,
+                      dsr_erase_result *result) {
+  if (int st = erase_mask_check(e, grid, mask, params)) return st;
+  CHECK_E(e);
+  const size_t n = (size_t)grid->nx * grid->ny * grid->nz;
+  Scratch sc("erase by mask: out of device memory for the staged mask");
+  uint8_t *dmask = nullptr;
+  if (int st = sc.get(&dmask, n)) return st;
+  HIP_TRY(hipMemcpyAsync(dmask, mask, n, hipMemcpyHostToDevice, e->stream));
+  dsr_erase_result r;
+  if (int st = dsr_erase_by_mask_dev(e, grid, dmask, params, &r)) return st;  // the one host wait: the staged mask is free afterwards
+  if (result) *result = r;
+  return DSR_OK;
+}
+
 }  // extern "C"
+
+// what the by-mask form refuses (dsr_components.h B.2) — also asked by dsr_despeckle (dsr_components.hip) before it queues anything
+int dsr_internal::erase_mask_check(const dsr_engine *e, const dsr_dense_grid *grid, const void *mask, const dsr_erase_params *params) {
+  if (!e) return fail(DSR_E_ARG, "erase by mask: null engine");
+  if (e->s.use_swapping) return fail(DSR_E_ARG, "erase by mask: engines with use_swapping are not supported");
+  if (!grid || !mask) return fail(DSR_E_ARG, "erase by mask: null grid or mask");
+  if (grid->nx < 1 || grid->ny < 1 || grid->nz < 1) return fail(DSR_E_ARG, "erase by mask: a grid needs at least one point per axis");
+  long long n = (long long)grid->nx * grid->ny;
+  if (n > 2147483647ll || (n *= grid->nz) > 2147483647ll) return fail(DSR_E_ARG, "erase by mask: more than 2^31 - 1 grid points");
+  if (!std::isfinite(grid->pitch) || grid->pitch <= 0.0f) return fail(DSR_E_ARG, "erase by mask: pitch must be finite and positive");
+  if (!rigid_transform(grid->grid_to_world_m)) return fail(DSR_E_ARG, "erase by mask: grid_to_world is not a rigid transform");
+  dsr_erase_params prm;
+  return erase_params(params, "erase by mask", prm);
+}

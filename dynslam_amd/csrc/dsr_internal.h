@@ -18,7 +18,10 @@
 //                     the ordering of the engines' streams, the one launch
 //   dsr_heightmap.hip a bird's-eye height map of a volume over a dense grid's columns (include/dsr_heightmap.h): the checks, the one launch
 //   dsr_erase.hip     erase and crop: a volume cleared by oriented boxes or by another volume's surface (include/dsr_erase.h): the checks,
-//                     the candidates, the one launch of k_erase.h, then the voxel GC's own commit and compaction
+//                     the candidates, the one launch of k_erase.h, then the voxel GC's own commit and compaction; and the same by a
+//                     per-point mask on a dense grid (dsr_erase_by_mask of include/dsr_components.h)
+//   dsr_components.hip connected components of a dense grid and despeckle (include/dsr_components.h): the checks, the launches of
+//                     k_components.h around one scan, the read-back; dsr_despeckle = export, label, erase by mask
 // Every KERNEL header (k_*.h) is included by exactly ONE of them: __global__ kernels have external linkage.  Headers that hold only
 // inline device functions (dsr_device.h, dsr_math.h, dsr_sample.h, k_dense_sample.h) are shared: any unit may include them.
 #pragma once
@@ -44,6 +47,7 @@
 using namespace dsr;
 
 struct dsr_dense_grid;           // include/dsr_dense.h
+struct dsr_erase_params;         // include/dsr_erase.h
 namespace dsr { struct DenseP; } // k_dense_sample.h
 namespace dsr { struct EraseRes; } // k_erase.h
 
@@ -389,6 +393,8 @@ int mesh_release(dsr_engine *e);
 // dsr_merge.hip: every DSR_E_ARG of a dsr_dense_grid (include/dsr_dense.h) for engine e; fills the export's kernel parameters g and the
 // number of grid points n.  importFields: fill_w and import_mode are checked too.  Also the height maps' check (dsr_heightmap.hip)
 int dense_grid_check(dsr_engine *e, const dsr_dense_grid *grid, const char *what, bool importFields, dsr::DenseP &g, long long &n);
+// dsr_erase.hip: every DSR_E_ARG of dsr_erase_by_mask (include/dsr_components.h B) — dsr_despeckle asks before it queues anything
+int erase_mask_check(const dsr_engine *e, const dsr_dense_grid *grid, const void *mask, const dsr_erase_params *params);
 // dsr_hostio.hip: is [p, p + bytes) inside a range the caller page-locked through dsr_pin_host_buffer?
 bool host_range_pinned(const void *p, size_t bytes);
 // dsr_profile.hip: div_short(x, b) == x / b for every x? (k_integrate.h; checked once per engine for its mu)

@@ -1,5 +1,6 @@
 // k_erase.h — erase and crop (include/dsr_erase.h): clear the voxels of a volume that lie inside (or outside) a
-// region given by oriented boxes or by another volume's surface.
+// region given by oriented boxes or by another volume's surface — or (include/dsr_components.h B) by a per-point mask
+// on a dense grid.
 //
 // ONE kernel, templated on the region predicate.  It takes the place of k_decay_blocks in the chain of a forced voxel GC pass
 // (candidates -> k_erase_blocks -> k_flag_count -> scan -> k_decay_commit -> k_live_keep_*; dsr_erase.hip): one wave per candidate
@@ -8,8 +9,9 @@
 //   prepare(pos)          all lanes of the wave, before the voxels of block `pos` are asked: false = NO voxel of the block is in the
 //                         region (wave-uniform; the block's voxels are then not asked);
 //   in_region(x, y, z)    is dst voxel (x, y, z) in the region (dsr_erase.h steps 1 and 2)?
-// tests/eraseref/erase_ref.cpp restates both serially.  The by-volume predicate samples src through dsr_sample.h (the box of src
-// blocks in the wave's 64 words of LDS, gather_corners with GATHER_WEIGHTED, trilinear8); nothing of k_raycast.h is used.
+// tests/eraseref/erase_ref.cpp restates the first two serially, tests/compref/comp_ref.cpp the by-mask one.  The by-volume predicate
+// samples src through dsr_sample.h (the box of src blocks in the wave's 64 words of LDS, gather_corners with GATHER_WEIGHTED,
+// trilinear8); nothing of k_raycast.h is used.
 #pragma once
 #include "dsr_sample.h"
 
@@ -120,6 +122,41 @@ struct EraseVolume {
     if (!gather_corners(vol, box, boxPtr, cache, q, GATHER_WEIGHTED, p.minW, c)) return false;
     const float g = (trilinear8(c.v, q.cx, q.cy, q.cz) / 32767.0f) * p.muSrc;
     return g <= p.margin;
+  }
+};
+
+// ------------------------------------------------------------------ the region, by a per-point mask on a dense grid
+
+// include/dsr_components.h B: a[4 i + j] = inv[4 j + i] as for a box, with inv the cofactor inverse of grid_to_world.  No per-block
+// shortcut: the predicate is one division per axis and one byte, and a block's mask bytes are a few cache lines.
+struct EraseMaskP {
+  float a[12];
+  float vs, pitch;
+  int nx, ny, nz;
+  const uint8_t *mask;
+};
+
+struct EraseMask {
+  typedef EraseMaskP Params;
+  const EraseMaskP &m;
+  __device__ __forceinline__ EraseMask(const EraseMaskP &m_, const SceneP &, int *, int) : m(m_) {}
+  __device__ __forceinline__ bool prepare(const short[3]) const { return true; }
+  // the grid index nearest to q / pitch on one axis, -1 outside [0, n) (and for a NaN)
+  __device__ __forceinline__ static int nearest(float q, float pitch, int n) {
+    const float f = floorf(q / pitch + 0.5f);
+    if (!(f >= 0.0f && f < 2147483648.0f)) return -1;
+    const int k = (int)f;
+    return k < n ? k : -1;
+  }
+  __device__ __forceinline__ bool in_region(int x, int y, int z) const {
+    const float px = (float)x * m.vs, py = (float)y * m.vs, pz = (float)z * m.vs;
+    const float *r = m.a;
+    const float q0 = ((r[0] * px + r[1] * py) + r[2] * pz) + r[3];
+    const float q1 = ((r[4] * px + r[5] * py) + r[6] * pz) + r[7];
+    const float q2 = ((r[8] * px + r[9] * py) + r[10] * pz) + r[11];
+    const int kx = nearest(q0, m.pitch, m.nx), ky = nearest(q1, m.pitch, m.ny), kz = nearest(q2, m.pitch, m.nz);
+    if ((kx | ky | kz) < 0) return false;
+    return m.mask[(size_t)kx + (size_t)m.nx * ((size_t)ky + (size_t)m.ny * (size_t)kz)] != 0;
   }
 };
 

@@ -148,6 +148,26 @@ def esdf_result_dict(res):
     return {k: int(getattr(res, k)) for k in ESDF_RESULT_KEYS}
 
 
+# struct dsr_component (include/dsr_components.h) as a numpy record, and the counts of dsr_comp_result
+COMPONENT_DTYPE = np.dtype([("root", "<i4"), ("points", "<i4"), ("lo", "<i4", (3,)), ("hi", "<i4", (3,)), ("flags", "<i4"),
+                            ("reserved", "<i4"), ("sum", "<i8", (3,))])
+assert COMPONENT_DTYPE.itemsize == 64
+COMP_RESULT_KEYS = ("occupied_points", "small_points", "components", "components_written", "small_components", "largest_points")
+
+
+def comp_params(api, connectivity=6, threshold=0.0, min_points=0, keep_border=True, min_w_depth=1):
+    """dsr_comp_params"""
+    p = _capi.CompParams()
+    api.components_default_params(C.byref(p))
+    p.connectivity, p.threshold, p.min_w_depth = int(connectivity), float(threshold), int(min_w_depth)
+    p.min_points, p.keep_border = int(min_points), int(bool(keep_border))
+    return p
+
+
+def comp_result_dict(res):
+    return {k: int(getattr(res, k)) for k in COMP_RESULT_KEYS}
+
+
 class Exchange:
     """The fused-preview exchange of include/dsr.h (`dsr_exchange_*`): layer buffers on every GPU this process drives, the RCCL
     all-gather between them (called by the library itself) and the composite.  `devices`: one process drives all GPUs, rank r
@@ -914,6 +934,128 @@ class EngineCore:
                                                       C.byref(res) if want_result else None))
         return self._erase_result(res) if want_result else None
 
+    # ---- connected components, erase by mask, despeckle (include/dsr_components.h; builder-defined)
+    def _comp_api(self):
+        if not hasattr(self, "_compapi"):
+            self._compapi = _capi.bind_components(self.api.lib, self.api.prefix)
+        if self._compapi is None:
+            raise DsrError(_capi.DSR_E_ARG, f"this backend ({self.api.prefix}*) has no include/dsr_components.h entry points")
+        return self._compapi
+
+    def components(self, shape, pitch, grid_to_world=None, *, connectivity=6, threshold=0.0, min_points=0, keep_border=True,
+                   capacity=4096, mu=None, sampling="nearest", min_w_depth=1, labels=True, mask=False, torch_out=False):
+        """The connected components of the volume's occupied points on the lattice of to_dense (shape = (nz, ny, nx), `pitch` metres,
+        grid_to_world) — dsr_components_export: the dense export into scratch planes, then the labelling.  A point is occupied when
+        it has data and its sdf (units of mu) is <= threshold; components join along the 6 axis neighbours or all 26.  Returns a
+        dict: "labels" int32 (nz, ny, nx), the component's id (its rank by smallest linear index) or -1; "table", a numpy record
+        array (COMPONENT_DTYPE: root, points, lo, hi, flags, sum) of the first min(components, capacity) components; with mask=True
+        "mask" uint8, 1 on the points of SMALL components (fewer than min_points points, and with keep_border not touching the
+        grid's border); and the counts of dsr_comp_result.  torch_out: labels and mask are torch tensors on the engine's GPU,
+        complete when the call returns.  Reads only."""
+        api = self._comp_api()
+        g = self._dense_grid(shape, pitch, grid_to_world, mu, sampling, min_w_depth)
+        p = comp_params(api, connectivity, threshold, min_points, keep_border, min_w_depth)
+        shape = (g.nz, g.ny, g.nx)
+        capacity = int(capacity)
+        res = _capi.CompResult()
+        out = {}
+        if torch_out:
+            import torch
+            dev = self._torch_device()
+            if labels:
+                out["labels"] = torch.empty(shape, dtype=torch.int32, device=dev)
+            if mask:
+                out["mask"] = torch.empty(shape, dtype=torch.uint8, device=dev)
+            table = torch.empty((max(capacity, 1), 8), dtype=torch.int64, device=dev)
+            self._check(api.components_export_dev(self._h, C.byref(g), C.byref(p), out["labels"].data_ptr() if labels else None,
+                                                  table.data_ptr() if capacity > 0 else None, capacity,
+                                                  out["mask"].data_ptr() if mask else None, C.byref(res)))
+            out["table"] = table[:res.components_written].cpu().numpy().view(COMPONENT_DTYPE).reshape(-1)
+        else:
+            if labels:
+                out["labels"] = np.empty(shape, np.int32)
+            if mask:
+                out["mask"] = np.empty(shape, np.uint8)
+            table = np.zeros(max(capacity, 1), COMPONENT_DTYPE)
+            self._check(api.components_export(self._h, C.byref(g), C.byref(p), _ptr(out["labels"]) if labels else None,
+                                              _ptr(table) if capacity > 0 else None, capacity, _ptr(out["mask"]) if mask else None,
+                                              C.byref(res)))
+            out["table"] = table[:res.components_written].copy()
+        out.update(comp_result_dict(res))
+        return out
+
+    def erase_by_mask(self, mask, pitch, grid_to_world=None, mode="inside", free_blocks=True, want_result=True):
+        """Clear the voxels whose nearest point of a dense grid (mask.shape = (nz, ny, nx), `pitch` metres, grid_to_world as to_dense)
+        has a non-zero mask byte (mode "inside"), or all others ("outside") — dsr_erase_by_mask.  mask: a numpy array of bytes or
+        bools, or a contiguous uint8 / bool torch tensor on the engine's GPU (ordered behind the current torch stream).  Emptied
+        blocks go back to the free list.  Returns the counts as a dict, or None with want_result=False: with a tensor on the GPU the
+        call is then only queued on the engine's stream (the tensor must stay alive until that work is done)."""
+        api = self._comp_api()
+        g = self._dense_grid(tuple(mask.shape), pitch, grid_to_world, None, "nearest", 1)
+        prm = self._erase_params(mode, free_blocks)
+        res = _capi.EraseResult()
+        if not isinstance(mask, np.ndarray) and hasattr(mask, "data_ptr"):
+            import torch
+            if not (mask.is_cuda and mask.device == self._torch_device() and mask.dtype in (torch.uint8, torch.bool) and mask.is_contiguous()):
+                raise DsrError(_capi.DSR_E_ARG, "erase_by_mask: the mask must be a contiguous uint8 or bool tensor on the engine's GPU")
+            self.wait_for_stream(torch.cuda.current_stream(self._torch_device()).cuda_stream)  # the tensor's producers first
+            self._check(api.erase_by_mask_dev(self._h, C.byref(g), mask.data_ptr(), C.byref(prm), C.byref(res) if want_result else None))
+        else:
+            m = np.ascontiguousarray(mask)
+            if m.dtype != np.uint8:
+                m = (m != 0).astype(np.uint8)
+            self._check(api.erase_by_mask(self._h, C.byref(g), _ptr(m), C.byref(prm), C.byref(res) if want_result else None))
+        return self._erase_result(res) if want_result else None
+
+    def despeckle_grid(self, box=None):
+        """The aligned grid despeckle() uses: (shape (nz, ny, nx), pitch, grid_to_world) with pitch = voxel_size, no rotation, every
+        voxel of the allocated blocks (or of `box` = (lo, hi), world metres) its own grid point, plus one point of margin on every
+        side.  None for an empty volume."""
+        vs = float(np.float32(self.settings.voxel_size))
+        if box is None:
+            b = self.allocated_bounds()
+            if b is None:
+                return None
+            lo, hi = b[0] * 8, b[1] * 8 + 7
+        else:
+            lo = np.floor(np.asarray(box[0], np.float64) / vs).astype(np.int64)
+            hi = np.ceil(np.asarray(box[1], np.float64) / vs).astype(np.int64)
+            if np.any(hi < lo):
+                raise DsrError(_capi.DSR_E_ARG, "despeckle: the box is empty")
+        lo, hi = lo - 1, hi + 1
+        n = hi - lo + 1
+        if int(n[0]) * int(n[1]) * int(n[2]) > 2**31 - 1 or np.any(n > 2**31 - 1):
+            raise DsrError(_capi.DSR_E_ARG, f"despeckle: the aligned grid over {'the allocated blocks' if box is None else 'the box'} has "
+                           f"{int(n[0])} x {int(n[1])} x {int(n[2])} points, more than 2^31 - 1: pass box=(lo, hi) in metres for a part "
+                           f"of the map (the whole reaches from {(lo * vs).tolist()} to {(hi * vs).tolist()})")
+        m = np.eye(4, dtype=np.float32)
+        m[:3, 3] = (lo.astype(np.float32) * np.float32(vs))
+        return (int(n[2]), int(n[1]), int(n[0])), vs, m
+
+    def despeckle(self, min_points, *, box=None, connectivity=6, threshold=0.0, keep_border=True, min_w_depth=1, free_blocks=True,
+                  want_result=True):
+        """Erase the volume's floaters — dsr_despeckle: the connected components (connectivity 6 or 26) of the voxels with data and
+        sdf <= threshold (units of mu) that have fewer than min_points voxels are cleared, their emptied blocks handed back.  Works on
+        the aligned grid of despeckle_grid(box): the whole map, or the part inside box = (lo, hi) in world metres; a component that
+        reaches that grid's border is kept unless keep_border is off.  Returns the counts of dsr_comp_result and dsr_erase_result in
+        one dict, or None with want_result=False: the call is then only queued on the engine's stream."""
+        api = self._comp_api()
+        grid = self.despeckle_grid(box)
+        if grid is None:
+            return dict.fromkeys(COMP_RESULT_KEYS + ("blocks_examined", "blocks_touched", "blocks_freed", "voxels_in_region", "voxels_erased"), 0) if want_result else None
+        shape, pitch, m = grid
+        g = self._dense_grid(shape, pitch, m, None, "nearest", min_w_depth)
+        p = comp_params(api, connectivity, threshold, min_points, keep_border, min_w_depth)
+        prm = self._erase_params("inside", free_blocks)
+        cres, eres = _capi.CompResult(), _capi.EraseResult()
+        self._check(api.despeckle(self._h, C.byref(g), C.byref(p), C.byref(prm), C.byref(cres) if want_result else None,
+                                  C.byref(eres) if want_result else None))
+        if not want_result:
+            return None
+        out = comp_result_dict(cres)
+        out.update(self._erase_result(eres))
+        return out
+
     # ---- the volume as a dense grid and back (include/dsr_dense.h, DESIGN.md §19; builder-defined)
     def _dense_api(self):
         if not hasattr(self, "_dapi"):
@@ -1434,6 +1576,21 @@ class InfiniTamDriver:
         transform src_to_dst (other's world -> this world), cut out of this one — the ghost of a vehicle that was fused into the map
         before it became a tracked instance.  Returns EngineCore.erase_by_volume's dict of counts."""
         return self.core.erase_by_volume(other.core, src_to_dst, margin=margin, **kwargs)
+
+    def LabelComponents(self, shape, pitch, grid_to_world=None, **kwargs):
+        """ITMMainEngine::LabelComponents (builder-defined, include/dsr_components.h): the connected components of the volume's
+        occupied points on a regular lattice — EngineCore.components' dict (INTEGRATION.md "components and despeckle")."""
+        return self.core.components(shape, pitch, grid_to_world, **kwargs)
+
+    def EraseMask(self, mask, pitch, grid_to_world=None, mode="inside", **kwargs):
+        """ITMMainEngine::EraseMask (builder-defined, include/dsr_components.h): the voxels whose nearest grid point has a non-zero
+        mask byte cleared, emptied blocks handed back — EngineCore.erase_by_mask's dict of counts."""
+        return self.core.erase_by_mask(mask, pitch, grid_to_world, mode=mode, **kwargs)
+
+    def Despeckle(self, min_points, **kwargs):
+        """ITMMainEngine::Despeckle (builder-defined, include/dsr_components.h): components of fewer than min_points voxels erased
+        from the map — EngineCore.despeckle's dict of counts."""
+        return self.core.despeckle(min_points, **kwargs)
 
     def CropToBox(self, box_to_world, half_extents, **kwargs):
         """ITMMainEngine::CropToBox (builder-defined, include/dsr_erase.h): everything outside the oriented box cleared and its blocks

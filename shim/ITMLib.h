@@ -34,6 +34,7 @@
 #include "../include/dsr_query.h"
 #include "../include/dsr_heightmap.h"
 #include "../include/dsr_erase.h"
+#include "../include/dsr_components.h"
 
 // The tracker's entry points are referenced WEAKLY: a host linked against a library without them (the CPU oracle's orc_* build
 // of the reference's hosts) still links, and ITMTrackingController::Track then throws as it did before the tracker existed.
@@ -82,6 +83,14 @@ int dsr_erase_boxes(dsr_engine *e, int n_boxes, const dsr_obox *boxes, const dsr
 int dsr_erase_by_volume(dsr_engine *dst, dsr_engine *src, const float src_to_dst_m[16], const dsr_erase_params *params,
                         dsr_erase_result *result) __attribute__((weak));
 void dsr_erase_default_params(dsr_erase_params *p) __attribute__((weak));
+// ... and components and despeckle (include/dsr_components.h): LabelComponents / EraseMask / Despeckle throw on a library without them
+void dsr_components_default_params(dsr_comp_params *p) __attribute__((weak));
+int dsr_components_export(dsr_engine *e, const dsr_dense_grid *grid, const dsr_comp_params *params, int32_t *labels,
+                          dsr_component *table, int32_t capacity, uint8_t *mask, dsr_comp_result *result) __attribute__((weak));
+int dsr_erase_by_mask(dsr_engine *e, const dsr_dense_grid *grid, const uint8_t *mask, const dsr_erase_params *params,
+                      dsr_erase_result *result) __attribute__((weak));
+int dsr_despeckle(dsr_engine *e, const dsr_dense_grid *grid, const dsr_comp_params *comp_params, const dsr_erase_params *erase_params,
+                  dsr_comp_result *comp_result, dsr_erase_result *erase_result) __attribute__((weak));
 // ... and the volume alignment's (include/dsr_align.h): AlignFrom throws on a library without it
 int dsr_align_volume(dsr_engine *dst, dsr_engine *src, const float init_src_to_dst_m[16], const dsr_align_params *params,
                      dsr_align_result *result, dsr_align_log_entry *log, int32_t log_capacity, int32_t *log_count) __attribute__((weak));
@@ -716,6 +725,39 @@ class ITMMainEngine {
     dsr_erase_params p = DefaultEraseParams();
     p.mode = DSR_ERASE_OUTSIDE;
     return EraseBoxes(1, &box, &p);
+  }
+  // BUILDER-DEFINED (include/dsr_components.h): the connected components of the volume's occupied points on the
+  // lattice `grid` describes (LabelComponents: host arrays of grid.nx * grid.ny * grid.nz labels / mask bytes and `capacity` table
+  // records, any of them null), the voxels whose nearest grid point has a non-zero mask byte cleared (EraseMask), and both in one
+  // call with the mask kept on the GPU (Despeckle: components of fewer than params.min_points points are erased).  Emptied blocks go
+  // back to the free list; raycast results are stale until the next Prepare.
+  static dsr_comp_params DefaultComponentParams() {
+    if (!dsr_components_default_params) throw std::runtime_error("this library has no components (include/dsr_components.h)");
+    dsr_comp_params p;
+    dsr_components_default_params(&p);
+    return p;
+  }
+  dsr_comp_result LabelComponents(const dsr_dense_grid &grid, const dsr_comp_params &params, int32_t *labels, dsr_component *table,
+                                  int32_t capacity, uint8_t *mask = nullptr) {
+    if (!dsr_components_export) throw std::runtime_error("this library has no components (include/dsr_components.h)");
+    dsr_comp_result res;
+    memset(&res, 0, sizeof res);
+    ITMLib::Engine::dsr_throw(dsr_components_export(engine_, &grid, &params, labels, table, capacity, mask, &res));
+    return res;
+  }
+  dsr_erase_result EraseMask(const dsr_dense_grid &grid, const uint8_t *mask, const dsr_erase_params *params = nullptr) {
+    if (!dsr_erase_by_mask) throw std::runtime_error("this library has no components (include/dsr_components.h)");
+    dsr_erase_result res;
+    memset(&res, 0, sizeof res);
+    ITMLib::Engine::dsr_throw(dsr_erase_by_mask(engine_, &grid, mask, params, &res));
+    return res;
+  }
+  dsr_erase_result Despeckle(const dsr_dense_grid &grid, const dsr_comp_params &params, dsr_comp_result *components = nullptr) {
+    if (!dsr_despeckle) throw std::runtime_error("this library has no components (include/dsr_components.h)");
+    dsr_erase_result res;
+    memset(&res, 0, sizeof res);
+    ITMLib::Engine::dsr_throw(dsr_despeckle(engine_, &grid, &params, nullptr, components, &res));
+    return res;
   }
   // BUILDER-DEFINED (include/dsr_dense.h): the volume sampled on the lattice `grid` describes into host planes of
   // grid.nx * grid.ny * grid.nz points (any of them may be null), and such planes written into the volume, allocating what it
