@@ -217,23 +217,47 @@ def preload_hip_runtime():
                 pass
 
 
-def bind(lib, prefix, allow_missing=False):
-    """Return a namespace of typed functions `prefix + name` looked up in `lib`.
-
-    Raises AttributeError when the library does not export a declared symbol (`allow_missing`: measurement tools that load
-    an OLDER build of the library for an A/B skip the entry points it lacks).
-    """
+def _typed(lib, prefix, signatures, allow_missing=False):
     ns = SimpleNamespace()
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in signatures.items():
         if allow_missing and not hasattr(lib, prefix + name):
             continue
         fn = getattr(lib, prefix + name)
         fn.restype = res
         fn.argtypes = args
         setattr(ns, name, fn)
+    return ns
+
+
+def bind(lib, prefix, allow_missing=False):
+    """Return a namespace of typed functions `prefix + name` looked up in `lib`.
+
+    Raises AttributeError when the library does not export a declared symbol (`allow_missing`: measurement tools that load
+    an OLDER build of the library for an A/B skip the entry points it lacks).
+    """
+    ns = _typed(lib, prefix, SIGNATURES, allow_missing)
     ns.lib = lib
     ns.prefix = prefix
     return ns
+
+
+def bind_table(lib, prefix, signatures, probe, versions, what):
+    """The entry points `prefix + name` of a header outside include/dsr.h (`what`) as a namespace of typed functions, or None when
+    `lib` lacks `prefix + probe`: the library has none of them (the CPU oracle, an older library).  versions: (version function,
+    expected value, the word for it in the message) — a library whose version differs is refused with an ImportError."""
+    if not hasattr(lib, prefix + probe):
+        return None
+    ns = _typed(lib, prefix, signatures)
+    for fn, expected, word in versions:
+        if getattr(ns, fn)() != expected:
+            raise ImportError(f"{word} ABI version mismatch ({what})")
+    return ns
+
+
+def bind_optional(lib, prefix, key):
+    """bind_table for the header that OPTIONAL_TABLES (at the end of this file) lists under `key`."""
+    t = OPTIONAL_TABLES[key]
+    return bind_table(lib, prefix, t["signatures"], t["probe"], t["versions"], t["what"])
 
 
 # ---- include/dsr_track.h: the ICP depth tracker.  A table of its own: dsr.h's SIGNATURES is what the CPU oracle mirrors
@@ -272,21 +296,6 @@ TRACK_SIGNATURES = {
 }
 
 
-def bind_track(lib, prefix):
-    """The tracker's entry points `prefix + name` in `lib`, or None when the library has no tracker (the CPU oracle)."""
-    if not hasattr(lib, prefix + "track"):
-        return None
-    ns = SimpleNamespace()
-    for name, (res, args) in TRACK_SIGNATURES.items():
-        fn = getattr(lib, prefix + name)
-        fn.restype = res
-        fn.argtypes = args
-        setattr(ns, name, fn)
-    if ns.track_abi_version() != TRACK_ABI_VERSION:
-        raise ImportError("tracker ABI version mismatch (include/dsr_track.h)")
-    return ns
-
-
 # ---- include/dsr_gc.h: the voxel GC of a batch's volumes.  A table of its own, like the tracker's (the oracle has no batch).
 GC_ABI_VERSION = 1  # == DSR_GC_ABI_VERSION
 
@@ -303,21 +312,6 @@ GC_SIGNATURES = {
     "gc_debug_alloc_list": (C.c_int, [_H, _P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "gc_debug_fifo": (C.c_int, [_H, C.POINTER(C.c_int32)]),
 }
-
-
-def bind_gc(lib, prefix):
-    """The batch GC's entry points `prefix + name` in `lib`, or None when the library has none (the CPU oracle)."""
-    if not hasattr(lib, prefix + "batch_decay"):
-        return None
-    ns = SimpleNamespace()
-    for name, (res, args) in GC_SIGNATURES.items():
-        fn = getattr(lib, prefix + name)
-        fn.restype = res
-        fn.argtypes = args
-        setattr(ns, name, fn)
-    if ns.gc_abi_version() != GC_ABI_VERSION:
-        raise ImportError("batch GC ABI version mismatch (include/dsr_gc.h)")
-    return ns
 
 
 # ---- include/dsr_eval.h: LIDAR-vs-depth accuracy scoring.  A table of its own, like the tracker's (the oracle has no evaluator).
@@ -370,21 +364,6 @@ EVAL_SIGNATURES = {
 }
 
 
-def bind_eval(lib, prefix):
-    """The evaluator's entry points `prefix + name` in `lib`, or None when the library has none (the CPU oracle)."""
-    if not hasattr(lib, prefix + "eval_lidar"):
-        return None
-    ns = SimpleNamespace()
-    for name, (res, args) in EVAL_SIGNATURES.items():
-        fn = getattr(lib, prefix + name)
-        fn.restype = res
-        fn.argtypes = args
-        setattr(ns, name, fn)
-    if ns.eval_abi_version() != EVAL_ABI_VERSION:
-        raise ImportError("evaluator ABI version mismatch (include/dsr_eval.h)")
-    return ns
-
-
 # ---- include/dsr_snapshot.h: save / restore of an engine's complete state.  A table of its own, like the tracker's (the oracle has
 # no snapshot).
 SNAPSHOT_ABI_VERSION = 1  # == DSR_SNAPSHOT_ABI_VERSION
@@ -411,21 +390,6 @@ SNAPSHOT_SIGNATURES = {
     "snapshot_free": (None, [C.c_void_p]),
     "snapshot_info": (C.c_int, [C.c_char_p, C.c_void_p, C.POINTER(SnapshotInfo)]),
 }
-
-
-def bind_snapshot(lib, prefix):
-    """The snapshot entry points `prefix + name` in `lib`, or None when the library has none (the CPU oracle)."""
-    if not hasattr(lib, prefix + "snapshot_save"):
-        return None
-    ns = SimpleNamespace()
-    for name, (res, args) in SNAPSHOT_SIGNATURES.items():
-        fn = getattr(lib, prefix + name)
-        fn.restype = res
-        fn.argtypes = args
-        setattr(ns, name, fn)
-    if ns.snapshot_abi_version() != SNAPSHOT_ABI_VERSION:
-        raise ImportError("snapshot ABI version mismatch (include/dsr_snapshot.h)")
-    return ns
 
 
 # ---- include/dsr_mesh.h: the complete mesh of a swapping engine.  A table of its own, like the snapshot's (the oracle has none).
@@ -458,23 +422,6 @@ MESH_SIGNATURES = {
 }
 
 
-def bind_mesh(lib, prefix):
-    """The complete mesher's entry points `prefix + name` in `lib`, or None when the library has none (the CPU oracle)."""
-    if not hasattr(lib, prefix + "mesh_scene_complete"):
-        return None
-    ns = SimpleNamespace()
-    for name, (res, args) in MESH_SIGNATURES.items():
-        fn = getattr(lib, prefix + name)
-        fn.restype = res
-        fn.argtypes = args
-        setattr(ns, name, fn)
-    if ns.mesh_abi_version() != MESH_ABI_VERSION:
-        raise ImportError("complete mesher ABI version mismatch (include/dsr_mesh.h)")
-    if ns.mesh_indexed_abi_version() != MESH_INDEXED_ABI_VERSION:
-        raise ImportError("indexed mesher ABI version mismatch (include/dsr_mesh.h)")
-    return ns
-
-
 # ---- include/dsr_merge.h: folding one volume into another at a rigid pose.  A table of its own, like the snapshot's (the oracle has none).
 MERGE_ABI_VERSION = 1  # == DSR_MERGE_ABI_VERSION
 
@@ -495,21 +442,6 @@ MERGE_SIGNATURES = {
     "merge_default_params": (None, [C.POINTER(MergeParams)]),
     "merge_volume": (C.c_int, [_H, _H, C.POINTER(C.c_float), C.POINTER(MergeParams), C.POINTER(MergeResult)]),
 }
-
-
-def bind_merge(lib, prefix):
-    """The merge entry points `prefix + name` in `lib`, or None when the library has none (the CPU oracle)."""
-    if not hasattr(lib, prefix + "merge_volume"):
-        return None
-    ns = SimpleNamespace()
-    for name, (res, args) in MERGE_SIGNATURES.items():
-        fn = getattr(lib, prefix + name)
-        fn.restype = res
-        fn.argtypes = args
-        setattr(ns, name, fn)
-    if ns.merge_abi_version() != MERGE_ABI_VERSION:
-        raise ImportError("merge ABI version mismatch (include/dsr_merge.h)")
-    return ns
 
 
 # ---- include/dsr_align.h: aligning one volume to another (SDF-to-SDF registration).  A table of its own, like the merge's (the oracle has none).
@@ -543,21 +475,6 @@ ALIGN_SIGNATURES = {
 }
 
 
-def bind_align(lib, prefix):
-    """The alignment entry points `prefix + name` in `lib`, or None when the library has none (the CPU oracle)."""
-    if not hasattr(lib, prefix + "align_volume"):
-        return None
-    ns = SimpleNamespace()
-    for name, (res, args) in ALIGN_SIGNATURES.items():
-        fn = getattr(lib, prefix + name)
-        fn.restype = res
-        fn.argtypes = args
-        setattr(ns, name, fn)
-    if ns.align_abi_version() != ALIGN_ABI_VERSION:
-        raise ImportError("align ABI version mismatch (include/dsr_align.h)")
-    return ns
-
-
 # ---- include/dsr_dense.h: a volume resampled into a dense grid and back.  A table of its own, like the merge's (the oracle has none).
 DENSE_ABI_VERSION = 1  # == DSR_DENSE_ABI_VERSION
 DENSE_NEAREST, DENSE_TRILINEAR = 0, 1  # DSR_DENSE_NEAREST / _TRILINEAR
@@ -585,21 +502,6 @@ DENSE_SIGNATURES = {
     "dense_import": (C.c_int, [_H, C.POINTER(DenseGrid), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DenseResult)]),
     "dense_import_dev": (C.c_int, [_H, C.POINTER(DenseGrid), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DenseResult)]),
 }
-
-
-def bind_dense(lib, prefix):
-    """The dense-grid entry points `prefix + name` in `lib`, or None when the library has none (the CPU oracle)."""
-    if not hasattr(lib, prefix + "dense_export"):
-        return None
-    ns = SimpleNamespace()
-    for name, (res, args) in DENSE_SIGNATURES.items():
-        fn = getattr(lib, prefix + name)
-        fn.restype = res
-        fn.argtypes = args
-        setattr(ns, name, fn)
-    if ns.dense_abi_version() != DENSE_ABI_VERSION:
-        raise ImportError("dense ABI version mismatch (include/dsr_dense.h)")
-    return ns
 
 
 # ---- include/dsr_esdf.h: an exact Euclidean signed distance field from a dense grid.  A table of its own, like the dense grids'.
@@ -630,21 +532,6 @@ ESDF_SIGNATURES = {
     "esdf_export": (C.c_int, _ESDF_EXPORT),
     "esdf_export_dev": (C.c_int, _ESDF_EXPORT),
 }
-
-
-def bind_esdf(lib, prefix):
-    """The ESDF entry points `prefix + name` in `lib`, or None when the library has none (the CPU oracle)."""
-    if not hasattr(lib, prefix + "esdf_export"):
-        return None
-    ns = SimpleNamespace()
-    for name, (res, args) in ESDF_SIGNATURES.items():
-        fn = getattr(lib, prefix + name)
-        fn.restype = res
-        fn.argtypes = args
-        setattr(ns, name, fn)
-    if ns.esdf_abi_version() != ESDF_ABI_VERSION:
-        raise ImportError("esdf ABI version mismatch (include/dsr_esdf.h)")
-    return ns
 
 
 # ---- include/dsr_query.h: distance, gradient and colour at arbitrary points.  A table of its own, like the ESDF's (the oracle has none).
@@ -680,21 +567,6 @@ QUERY_SIGNATURES = {
 }
 
 
-def bind_query(lib, prefix):
-    """The point-query entry points `prefix + name` in `lib`, or None when the library has none (the CPU oracle)."""
-    if not hasattr(lib, prefix + "query_points"):
-        return None
-    ns = SimpleNamespace()
-    for name, (res, args) in QUERY_SIGNATURES.items():
-        fn = getattr(lib, prefix + name)
-        fn.restype = res
-        fn.argtypes = args
-        setattr(ns, name, fn)
-    if ns.query_abi_version() != QUERY_ABI_VERSION:
-        raise ImportError("query ABI version mismatch (include/dsr_query.h)")
-    return ns
-
-
 # ---- include/dsr_heightmap.h: a bird's-eye height map over a dense grid's columns.  A table of its own, like the queries' (the oracle has none).
 HEIGHTMAP_ABI_VERSION = 1  # == DSR_HEIGHTMAP_ABI_VERSION
 HEIGHTMAP_HAS_DATA, HEIGHTMAP_HAS_GROUND, HEIGHTMAP_HAS_CEILING, HEIGHTMAP_MULTI, HEIGHTMAP_OBSTACLE = 1, 2, 4, 8, 16  # DSR_HEIGHTMAP_* flag bits
@@ -725,21 +597,6 @@ HEIGHTMAP_SIGNATURES = {
 }
 
 
-def bind_heightmap(lib, prefix):
-    """The height-map entry points `prefix + name` in `lib`, or None when the library has none (the CPU oracle)."""
-    if not hasattr(lib, prefix + "heightmap_export"):
-        return None
-    ns = SimpleNamespace()
-    for name, (res, args) in HEIGHTMAP_SIGNATURES.items():
-        fn = getattr(lib, prefix + name)
-        fn.restype = res
-        fn.argtypes = args
-        setattr(ns, name, fn)
-    if ns.heightmap_abi_version() != HEIGHTMAP_ABI_VERSION:
-        raise ImportError("heightmap ABI version mismatch (include/dsr_heightmap.h)")
-    return ns
-
-
 # ---- include/dsr_erase.h: erase and crop — a volume cleared by oriented boxes or by another volume's surface.  A table of its own (the oracle has none).
 ERASE_ABI_VERSION = 1  # == DSR_ERASE_ABI_VERSION
 ERASE_INSIDE, ERASE_OUTSIDE = 0, 1  # DSR_ERASE_*
@@ -768,21 +625,6 @@ ERASE_SIGNATURES = {
     "erase_boxes": (C.c_int, [_H, C.c_int, C.POINTER(EraseBox), C.POINTER(EraseParams), C.POINTER(EraseResult)]),
     "erase_by_volume": (C.c_int, [_H, _H, C.POINTER(C.c_float), C.POINTER(EraseParams), C.POINTER(EraseResult)]),
 }
-
-
-def bind_erase(lib, prefix):
-    """The erase entry points `prefix + name` in `lib`, or None when the library has none (the CPU oracle)."""
-    if not hasattr(lib, prefix + "erase_boxes"):
-        return None
-    ns = SimpleNamespace()
-    for name, (res, args) in ERASE_SIGNATURES.items():
-        fn = getattr(lib, prefix + name)
-        fn.restype = res
-        fn.argtypes = args
-        setattr(ns, name, fn)
-    if ns.erase_abi_version() != ERASE_ABI_VERSION:
-        raise ImportError("erase ABI version mismatch (include/dsr_erase.h)")
-    return ns
 
 
 # ---- include/dsr_components.h: connected components of a dense grid, erase by a per-point mask, despeckle.  A table of its own (the oracle has none).
@@ -827,17 +669,45 @@ COMPONENTS_SIGNATURES = {
 }
 
 
-def bind_components(lib, prefix):
-    """The entry points of include/dsr_components.h `prefix + name` in `lib`, or None when the library has none (an older library, the
-    CPU oracle)."""
-    if not hasattr(lib, prefix + "components_export"):
-        return None
-    ns = SimpleNamespace()
-    for name, (res, args) in COMPONENTS_SIGNATURES.items():
-        fn = getattr(lib, prefix + name)
-        fn.restype = res
-        fn.argtypes = args
-        setattr(ns, name, fn)
-    if ns.components_abi_version() != COMPONENTS_ABI_VERSION:
-        raise ImportError("components ABI version mismatch (include/dsr_components.h)")
-    return ns
+# ---- the tables above by name: the ONE place that maps a name to a header's signatures, its probe symbol, its version checks and
+# what a caller is told when the library lacks it (engine.optional_api caches the bound namespaces under these names)
+def _table(signatures, probe, what, versions, missing=None):
+    return {"signatures": signatures, "probe": probe, "what": what,
+            "versions": tuple((f"{fn}_abi_version", expected, word) for fn, expected, word in versions),
+            "missing": missing or f"no {what} entry points"}
+
+
+OPTIONAL_TABLES = {
+    "track": _table(TRACK_SIGNATURES, "track", "include/dsr_track.h", [("track", TRACK_ABI_VERSION, "tracker")],
+                    "no ICP tracker: dsr_track is a libdsr_hip.so entry point"),
+    "gc": _table(GC_SIGNATURES, "batch_decay", "include/dsr_gc.h", [("gc", GC_ABI_VERSION, "batch GC")]),
+    "eval": _table(EVAL_SIGNATURES, "eval_lidar", "include/dsr_eval.h", [("eval", EVAL_ABI_VERSION, "evaluator")]),
+    "snapshot": _table(SNAPSHOT_SIGNATURES, "snapshot_save", "include/dsr_snapshot.h", [("snapshot", SNAPSHOT_ABI_VERSION, "snapshot")]),
+    "mesh": _table(MESH_SIGNATURES, "mesh_scene_complete", "include/dsr_mesh.h",
+                   [("mesh", MESH_ABI_VERSION, "complete mesher"), ("mesh_indexed", MESH_INDEXED_ABI_VERSION, "indexed mesher")]),
+    "merge": _table(MERGE_SIGNATURES, "merge_volume", "include/dsr_merge.h", [("merge", MERGE_ABI_VERSION, "merge")]),
+    "align": _table(ALIGN_SIGNATURES, "align_volume", "include/dsr_align.h", [("align", ALIGN_ABI_VERSION, "align")]),
+    "dense": _table(DENSE_SIGNATURES, "dense_export", "include/dsr_dense.h", [("dense", DENSE_ABI_VERSION, "dense")]),
+    "esdf": _table(ESDF_SIGNATURES, "esdf_export", "include/dsr_esdf.h", [("esdf", ESDF_ABI_VERSION, "esdf")]),
+    "query": _table(QUERY_SIGNATURES, "query_points", "include/dsr_query.h", [("query", QUERY_ABI_VERSION, "query")]),
+    "heightmap": _table(HEIGHTMAP_SIGNATURES, "heightmap_export", "include/dsr_heightmap.h", [("heightmap", HEIGHTMAP_ABI_VERSION, "heightmap")]),
+    "erase": _table(ERASE_SIGNATURES, "erase_boxes", "include/dsr_erase.h", [("erase", ERASE_ABI_VERSION, "erase")]),
+    "components": _table(COMPONENTS_SIGNATURES, "components_export", "include/dsr_components.h",
+                         [("components", COMPONENTS_ABI_VERSION, "components")]),
+}
+
+
+# the binders by their earlier names (tests and tools call them)
+def bind_track(lib, prefix): return bind_optional(lib, prefix, "track")
+def bind_gc(lib, prefix): return bind_optional(lib, prefix, "gc")
+def bind_eval(lib, prefix): return bind_optional(lib, prefix, "eval")
+def bind_snapshot(lib, prefix): return bind_optional(lib, prefix, "snapshot")
+def bind_mesh(lib, prefix): return bind_optional(lib, prefix, "mesh")
+def bind_merge(lib, prefix): return bind_optional(lib, prefix, "merge")
+def bind_align(lib, prefix): return bind_optional(lib, prefix, "align")
+def bind_dense(lib, prefix): return bind_optional(lib, prefix, "dense")
+def bind_esdf(lib, prefix): return bind_optional(lib, prefix, "esdf")
+def bind_query(lib, prefix): return bind_optional(lib, prefix, "query")
+def bind_heightmap(lib, prefix): return bind_optional(lib, prefix, "heightmap")
+def bind_erase(lib, prefix): return bind_optional(lib, prefix, "erase")
+def bind_components(lib, prefix): return bind_optional(lib, prefix, "components")

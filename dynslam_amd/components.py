@@ -8,25 +8,16 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from .engine import COMPONENT_DTYPE, DsrError, _ptr, comp_params, comp_result_dict, load_hip_api
-
-_api = None
+from .engine import COMPONENT_DTYPE, DsrError, _ptr, comp_params, comp_result_dict, load_hip_api, optional_api
 
 
 def _comp_api():
-    global _api
-    if _api is None:
-        hip = load_hip_api()
-        _api = _capi.bind_components(hip.lib, hip.prefix)
-        if _api is None:
-            raise DsrError(_capi.DSR_E_ARG, "libdsr_hip.so has no include/dsr_components.h entry points")
-        _api.last_error = hip.last_error
-    return _api
+    return optional_api(load_hip_api(), "components", "libdsr_hip.so has no include/dsr_components.h entry points")
 
 
-def _check(api, status):
+def _check(status):
     if status != _capi.DSR_OK:
-        msg = api.last_error()
+        msg = load_hip_api().last_error()
         raise DsrError(status, msg.decode() if msg else "")
 
 
@@ -65,11 +56,11 @@ def components_from_planes(sdf=None, w_depth=None, *, occ=None, connectivity=6, 
                 out["mask"] = torch.empty(shape, dtype=torch.uint8, device=src.device)
             dtable = torch.empty((max(capacity, 1), 8), dtype=torch.int64, device=src.device)
             stream = torch.cuda.current_stream(src.device).cuda_stream
-            _check(api, api.components_from_planes_dev(src.device.index, C.c_void_p(stream), nx, ny, nz,
-                                                       None if sdf is None else sdf.data_ptr(), None if w_depth is None else w_depth.data_ptr(),
-                                                       None if occ is None else occ.data_ptr(), C.byref(p),
-                                                       out["labels"].data_ptr() if labels else None, dtable.data_ptr() if capacity > 0 else None,
-                                                       capacity, out["mask"].data_ptr() if mask else None, C.byref(res) if wait else None))
+            _check(api.components_from_planes_dev(src.device.index, C.c_void_p(stream), nx, ny, nz,
+                                                  None if sdf is None else sdf.data_ptr(), None if w_depth is None else w_depth.data_ptr(),
+                                                  None if occ is None else occ.data_ptr(), C.byref(p),
+                                                  out["labels"].data_ptr() if labels else None, dtable.data_ptr() if capacity > 0 else None,
+                                                  capacity, out["mask"].data_ptr() if mask else None, C.byref(res) if wait else None))
         if not wait:
             if table:
                 out["table"] = dtable[:capacity]
@@ -90,9 +81,9 @@ def components_from_planes(sdf=None, w_depth=None, *, occ=None, connectivity=6, 
         if mask:
             out["mask"] = np.empty(shape, np.uint8)
         htable = np.zeros(max(capacity, 1), COMPONENT_DTYPE)
-        _check(api, api.components_from_planes(int(device), None, nx, ny, nz, *(None if a is None else _ptr(a) for a in planes), C.byref(p),
-                                               _ptr(out["labels"]) if labels else None, _ptr(htable) if capacity > 0 else None, capacity,
-                                               _ptr(out["mask"]) if mask else None, C.byref(res)))
+        _check(api.components_from_planes(int(device), None, nx, ny, nz, *(None if a is None else _ptr(a) for a in planes), C.byref(p),
+                                          _ptr(out["labels"]) if labels else None, _ptr(htable) if capacity > 0 else None, capacity,
+                                          _ptr(out["mask"]) if mask else None, C.byref(res)))
         if table:
             out["table"] = htable[:res.components_written].copy()
     out.update(comp_result_dict(res))

@@ -6,7 +6,7 @@
 // the union-find's parent array (4 bytes per point; the caller's labels plane where there is one), the per-root counts (4), the
 // ranks (4), the scan's workspace and 8 KiB of counters; the forms that must not wait take them stream-ordered.  dsr_erase_by_mask
 // lives next to the other region predicates (dsr_erase.hip, k_erase.h); dsr_despeckle chains export, labelling and that erase here.
-#include "dsr_internal.h"
+#include "dsr_hostcall.h"
 using namespace dsr_internal;
 #include <hipcub/hipcub.hpp>
 
@@ -16,8 +16,6 @@ using namespace dsr_internal;
 static_assert(sizeof(dsr_component) == 64 && sizeof(dsr_comp_params) == 32 && sizeof(dsr_comp_result) == 48, "dsr_components.h layout");
 
 namespace {
-
-bool misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 
 struct CompCall { CompP p; long long n; };
 constexpr int kCompMaxGrid = 16384, kCompMaxGridRoots = 1024;  // workgroups of 4 waves
@@ -33,14 +31,6 @@ int comp_check_params(const dsr_comp_params *params, int32_t capacity, const cha
   return DSR_OK;
 }
 
-int comp_check_shape(int32_t nx, int32_t ny, int32_t nz, const char *what, long long *n) {
-  const std::string w(what);
-  if (nx < 1 || ny < 1 || nz < 1) return fail(DSR_E_ARG, w + ": a grid needs at least one point per axis");
-  *n = (long long)nx * ny;
-  if (*n > 2147483647ll || (*n *= nz) > 2147483647ll) return fail(DSR_E_ARG, w + ": more than 2^31 - 1 grid points");
-  return DSR_OK;
-}
-
 void comp_fill(CompCall &c, int32_t nx, int32_t ny, int32_t nz, long long n, const dsr_comp_params *params, const void *table, int32_t capacity) {
   c.p = CompP{};
   c.p.nx = nx; c.p.ny = ny; c.p.nz = nz;
@@ -51,16 +41,6 @@ void comp_fill(CompCall &c, int32_t nx, int32_t ny, int32_t nz, long long n, con
   c.p.capacity = table ? capacity : 0;
   c.p.threshold = params->threshold;
   c.n = n;
-}
-
-template <class... Args, class... Params>
-void comp_launch(dsr_engine *e, const char *name, hipStream_t stream, void (*kernel)(Params...), int grid, Args... args) {
-  if (e) {
-    ProfScope ps(e, name);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, stream, args...);
-  } else {
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, stream, args...);
-  }
 }
 
 typedef hipcub::TransformInputIterator<int, CompIsRoot, hipcub::CountingInputIterator<int>> CompRootIter;
@@ -83,20 +63,15 @@ int comp_queue(dsr_engine *e, hipStream_t stream, Scratch &sc, const CompCall &c
   if (const char *env = getenv("DSR_GRID_COMPONENTS"))
     if (atoi(env) >= 1) grid = gridRoots = std::min(atoi(env), 65535);
   if (counters) HIP_TRY(hipMemsetAsync(counters, 0, kCompCounterWords * sizeof *counters, stream));
-  comp_launch(e, "comp_init", stream, k_comp_init, grid, p, sdf, w, occ, parent, cnt);
-  comp_launch(e, "comp_join", stream, k_comp_join, grid, p, parent);
-  comp_launch(e, "comp_flatten", stream, k_comp_flatten, grid, p, parent, cnt);
-  if (e) {
-    ProfScope ps(e, "comp_scan");
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tmpBytes, roots, rank, (int)c.n, stream));
-  } else {
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tmpBytes, roots, rank, (int)c.n, stream));
-  }
+  launch_on(e, stream, "comp_init", k_comp_init, grid, p, sdf, w, occ, parent, cnt);
+  launch_on(e, stream, "comp_join", k_comp_join, grid, p, parent);
+  launch_on(e, stream, "comp_flatten", k_comp_flatten, grid, p, parent, cnt);
+  HIP_TRY(scoped_on(e, "comp_scan", [&] { return hipcub::DeviceScan::ExclusiveSum(tmp, tmpBytes, roots, rank, (int)c.n, stream); }));
   if (counters || (table && p.capacity > 0))
-    comp_launch(e, "comp_roots", stream, k_comp_roots, gridRoots, p, (const int32_t *)parent, (const uint32_t *)cnt, (const int32_t *)rank,
+    launch_on(e, stream, "comp_roots", k_comp_roots, gridRoots, p, (const int32_t *)parent, (const uint32_t *)cnt, (const int32_t *)rank,
                 table, counters);
   if (labels || mask || (table && p.capacity > 0))
-    comp_launch(e, "comp_final", stream, k_comp_final, grid, p, (const int32_t *)parent, (const uint32_t *)cnt, (const int32_t *)rank, labels,
+    launch_on(e, stream, "comp_final", k_comp_final, grid, p, (const int32_t *)parent, (const uint32_t *)cnt, (const int32_t *)rank, labels,
                 p.capacity > 0 ? table : nullptr, mask);
   HIP_TRY(hipGetLastError());
   return DSR_OK;
@@ -118,45 +93,34 @@ void comp_fill_result(dsr_comp_result *result, const unsigned long long *h, int 
   result->largest_points = (int32_t)sum[CC_LARGEST];
 }
 
-// the labelling with device planes on `stream`; result == null: queued only
-int comp_run_dev(dsr_engine *e, hipStream_t stream, Scratch &sc, const CompCall &c, const float *sdf, const uint8_t *w, const uint8_t *occ,
-                 int32_t *labels, dsr_component *table, uint8_t *mask, dsr_comp_result *result) {
-  if (!result) return comp_queue(e, stream, sc, c, sdf, w, occ, labels, table, mask, nullptr);
-  unsigned long long *counters;
-  std::vector<unsigned long long> h(kCompCounterWords);
-  if (int st = sc.get(&counters, kCompCounterWords)) return st;
-  if (int st = comp_queue(e, stream, sc, c, sdf, w, occ, labels, table, mask, counters)) return st;
-  HIP_TRY(hipMemcpyAsync(h.data(), counters, kCompCounterWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));  // the one host wait
-  comp_fill_result(result, h.data(), c.p.capacity);
+// the labelling with device planes on h's stream; result == null: queued only
+int comp_run_dev(dsr_engine *e, HostCall &h, const CompCall &c, const float *sdf, const uint8_t *w, const uint8_t *occ, int32_t *labels,
+                 dsr_component *table, uint8_t *mask, dsr_comp_result *result) {
+  if (!result) return comp_queue(e, h.stream, h.sc, c, sdf, w, occ, labels, table, mask, nullptr);
+  std::vector<unsigned long long> hc(kCompCounterWords);
+  unsigned long long *counters = h.out(hc.data(), kCompCounterWords);
+  int st;
+  if ((st = h.begin()) || (st = comp_queue(e, h.stream, h.sc, c, sdf, w, occ, labels, table, mask, counters)) || (st = h.finish())) return st;
+  comp_fill_result(result, hc.data(), c.p.capacity);
   return DSR_OK;
 }
 
-// the labelling with device inputs and HOST outputs on `stream`: staged outputs, the copies back, the one host wait
-int comp_run_host_out(dsr_engine *e, hipStream_t stream, Scratch &sc, const CompCall &c, const float *sdf, const uint8_t *w, const uint8_t *occ,
-                      int32_t *labels, dsr_component *table, uint8_t *mask, dsr_comp_result *result) {
+// the labelling with device inputs (or the staged ones of h) and HOST outputs: staged outputs, the copies back, the one host wait
+int comp_run_host_out(dsr_engine *e, HostCall &h, const CompCall &c, const float *sdf, const uint8_t *w, const uint8_t *occ, int32_t *labels,
+                      dsr_component *table, uint8_t *mask, dsr_comp_result *result) {
   const size_t n = (size_t)c.n;
-  int32_t *dlabels = nullptr;
-  dsr_component *dtable = nullptr;
-  uint8_t *dmask = nullptr;
-  unsigned long long *counters;
-  std::vector<unsigned long long> h(kCompCounterWords);
-  const bool wantTable = table && c.p.capacity > 0;
-  std::vector<dsr_component> htable(wantTable ? (size_t)c.p.capacity : 0);
+  std::vector<unsigned long long> hc(kCompCounterWords);
+  // the table comes back into a buffer of ours: only the records that exist are the caller's to see (step 5)
+  std::vector<dsr_component> htable(table && c.p.capacity > 0 ? (size_t)c.p.capacity : 0);
+  int32_t *dlabels = h.out(labels, n);
+  uint8_t *dmask = h.out(mask, n);
+  dsr_component *dtable = htable.empty() ? nullptr : h.out(htable.data(), htable.size());
+  unsigned long long *counters = h.out(hc.data(), kCompCounterWords);
   int st;
-  if ((labels && (st = sc.get(&dlabels, n))) || (wantTable && (st = sc.get(&dtable, (size_t)c.p.capacity))) || (mask && (st = sc.get(&dmask, n))) ||
-      (st = sc.get(&counters, kCompCounterWords)))
-    return st;
-  if ((st = comp_queue(e, stream, sc, c, sdf, w, occ, dlabels, dtable, dmask, counters))) return st;
-  if (labels) HIP_TRY(hipMemcpyAsync(labels, dlabels, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-  if (mask) HIP_TRY(hipMemcpyAsync(mask, dmask, n, hipMemcpyDeviceToHost, stream));
-  if (wantTable) HIP_TRY(hipMemcpyAsync(htable.data(), dtable, htable.size() * sizeof(dsr_component), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(h.data(), counters, kCompCounterWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));  // the one host wait
+  if ((st = h.begin()) || (st = comp_queue(e, h.stream, h.sc, c, sdf, w, occ, dlabels, dtable, dmask, counters)) || (st = h.finish())) return st;
   dsr_comp_result r;
-  comp_fill_result(&r, h.data(), c.p.capacity);
-  // only the records that exist are the caller's to see (step 5)
-  if (wantTable && r.components_written > 0) memcpy(table, htable.data(), (size_t)r.components_written * sizeof(dsr_component));
+  comp_fill_result(&r, hc.data(), c.p.capacity);
+  if (r.components_written > 0 && !htable.empty()) memcpy(table, htable.data(), (size_t)r.components_written * sizeof(dsr_component));
   if (result) *result = r;
   return DSR_OK;
 }
@@ -165,7 +129,7 @@ int comp_run_host_out(dsr_engine *e, hipStream_t stream, Scratch &sc, const Comp
 int comp_engine_setup(dsr_engine *e, const dsr_dense_grid *grid, const dsr_comp_params *params, int32_t capacity, const char *what, long long *n) {
   if (int st = comp_check_params(params, capacity, what)) return st;
   if (!e || !grid) return fail(DSR_E_ARG, std::string(what) + ": null argument");
-  return comp_check_shape(grid->nx, grid->ny, grid->nz, what, n);
+  return grid_points_check(grid->nx, grid->ny, grid->nz, what, n);
 }
 
 // dsr_dense_export_dev into scratch planes (it refuses what the dense grids refuse, before anything is queued), then the call's fields
@@ -202,19 +166,16 @@ int dsr_components_from_planes_dev(int device, void *hip_stream, int32_t nx, int
   long long n = 0;
   if (int st = comp_check_params(params, capacity, what)) return st;
   if ((sdf_dev != nullptr) == (occ_dev != nullptr)) return fail(DSR_E_ARG, "components from planes: exactly one of sdf and occ is needed");
-  if (int st = comp_check_shape(nx, ny, nz, what, &n)) return st;
+  if (int st = grid_points_check(nx, ny, nz, what, &n)) return st;
   if (misaligned(sdf_dev, 4) || misaligned(labels_dev, 4) || misaligned(table_dev, 8))
     return fail(DSR_E_ARG, "components from planes: the sdf and labels planes must be 4-byte aligned, the table 8-byte aligned");
   CompCall c;
   comp_fill(c, nx, ny, nz, n, params, table_dev, capacity);
   HIP_TRY(hipSetDevice(device));
   hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  if (!result) {
-    Scratch sc("components: out of device memory for the temporaries", stream);  // stream-ordered: neither taken nor released with a wait
-    return comp_run_dev(nullptr, stream, sc, c, sdf_dev, occ_dev ? nullptr : w_depth_dev, occ_dev, labels_dev, table_dev, mask_dev, nullptr);
-  }
-  Scratch sc("components: out of device memory for the temporaries");
-  return comp_run_dev(nullptr, stream, sc, c, sdf_dev, occ_dev ? nullptr : w_depth_dev, occ_dev, labels_dev, table_dev, mask_dev, result);
+  Scratch sc("components: out of device memory for the temporaries", stream, !result);  // queued only: neither taken nor released with a wait
+  HostCall h(sc, stream);
+  return comp_run_dev(nullptr, h, c, sdf_dev, occ_dev ? nullptr : w_depth_dev, occ_dev, labels_dev, table_dev, mask_dev, result);
 }
 
 int dsr_components_from_planes(int device, void *hip_stream, int32_t nx, int32_t ny, int32_t nz, const float *sdf,
@@ -224,25 +185,17 @@ int dsr_components_from_planes(int device, void *hip_stream, int32_t nx, int32_t
   long long nn = 0;
   if (int st = comp_check_params(params, capacity, what)) return st;
   if ((sdf != nullptr) == (occ != nullptr)) return fail(DSR_E_ARG, "components from planes: exactly one of sdf and occ is needed");
-  if (int st = comp_check_shape(nx, ny, nz, what, &nn)) return st;
+  if (int st = grid_points_check(nx, ny, nz, what, &nn)) return st;
   const size_t n = (size_t)nn;
   CompCall c;
   comp_fill(c, nx, ny, nz, nn, params, table, capacity);
   HIP_TRY(hipSetDevice(device));
   hipStream_t stream = static_cast<hipStream_t>(hip_stream);
   Scratch sc("components: out of device memory for the staging buffers");
-  float *dsdf = nullptr;
-  uint8_t *dw = nullptr, *docc = nullptr;
-  int st;
-  if (sdf) {
-    if ((st = sc.get(&dsdf, n)) || (w_depth && (st = sc.get(&dw, n)))) return st;
-    HIP_TRY(hipMemcpyAsync(dsdf, sdf, n * sizeof(float), hipMemcpyHostToDevice, stream));
-    if (w_depth) HIP_TRY(hipMemcpyAsync(dw, w_depth, n, hipMemcpyHostToDevice, stream));
-  } else {
-    if ((st = sc.get(&docc, n))) return st;
-    HIP_TRY(hipMemcpyAsync(docc, occ, n, hipMemcpyHostToDevice, stream));
-  }
-  return comp_run_host_out(nullptr, stream, sc, c, dsdf, dw, docc, labels, table, mask, result);
+  HostCall h(sc, stream);
+  const float *dsdf = h.in(sdf, n);
+  const uint8_t *dw = sdf ? h.in(w_depth, n) : nullptr, *docc = h.in(occ, n);
+  return comp_run_host_out(nullptr, h, c, dsdf, dw, docc, labels, table, mask, result);
 }
 
 int dsr_components_export_dev(dsr_engine *e, const dsr_dense_grid *grid, const dsr_comp_params *params, int32_t *labels_dev,
@@ -255,14 +208,10 @@ int dsr_components_export_dev(dsr_engine *e, const dsr_dense_grid *grid, const d
   CompCall c;
   float *sdf;
   uint8_t *w;
-  if (!result) {
-    Scratch sc("components export: out of device memory for the temporaries", e->stream);
-    if (int st = comp_engine_export(e, grid, params, sc, n, table_dev, capacity, c, &sdf, &w)) return st;
-    return comp_run_dev(e, e->stream, sc, c, sdf, w, nullptr, labels_dev, table_dev, mask_dev, nullptr);
-  }
-  Scratch sc("components export: out of device memory for the temporaries");
+  Scratch sc("components export: out of device memory for the temporaries", e->stream, !result);
+  HostCall h(sc, e->stream);
   if (int st = comp_engine_export(e, grid, params, sc, n, table_dev, capacity, c, &sdf, &w)) return st;
-  return comp_run_dev(e, e->stream, sc, c, sdf, w, nullptr, labels_dev, table_dev, mask_dev, result);
+  return comp_run_dev(e, h, c, sdf, w, nullptr, labels_dev, table_dev, mask_dev, result);
 }
 
 int dsr_components_export(dsr_engine *e, const dsr_dense_grid *grid, const dsr_comp_params *params, int32_t *labels,
@@ -274,8 +223,9 @@ int dsr_components_export(dsr_engine *e, const dsr_dense_grid *grid, const dsr_c
   float *sdf;
   uint8_t *w;
   Scratch sc("components export: out of device memory for the staging buffers");
+  HostCall h(sc, e->stream);
   if (int st = comp_engine_export(e, grid, params, sc, n, table, capacity, c, &sdf, &w)) return st;
-  return comp_run_host_out(e, e->stream, sc, c, sdf, w, nullptr, labels, table, mask, result);
+  return comp_run_host_out(e, h, c, sdf, w, nullptr, labels, table, mask, result);
 }
 
 int dsr_despeckle(dsr_engine *e, const dsr_dense_grid *grid, const dsr_comp_params *comp_params, const dsr_erase_params *erase_params,

@@ -6,7 +6,7 @@
 //   engine_free_flagged   the GC's own flag count, scan, commit (tombstones, the ordered hand-back of blocks) and the compaction of
 //                         the live visible list;
 // then, only when the caller wants the counts, ONE host wait: the read-back of the result record.  Nothing is allocated.
-#include "dsr_internal.h"
+#include "dsr_hostcall.h"
 using namespace dsr_internal;
 
 #include "dsr_math.h"
@@ -166,9 +166,9 @@ int dsr_erase_by_mask(dsr_engine *e, const dsr_dense_grid *grid, const uint8_t *
   CHECK_E(e);
   const size_t n = (size_t)grid->nx * grid->ny * grid->nz;
   Scratch sc("erase by mask: out of device memory for the staged mask");
-  uint8_t *dmask = nullptr;
-  if (int st = sc.get(&dmask, n)) return st;
-  HIP_TRY(hipMemcpyAsync(dmask, mask, n, hipMemcpyHostToDevice, e->stream));
+  HostCall h(sc, e->stream);
+  const uint8_t *dmask = h.in(mask, n);
+  if (int st = h.begin()) return st;
   dsr_erase_result r;
   if (int st = dsr_erase_by_mask_dev(e, grid, dmask, params, &r)) return st;  // the one host wait: the staged mask is free afterwards
   if (result) *result = r;
@@ -182,9 +182,8 @@ int dsr_internal::erase_mask_check(const dsr_engine *e, const dsr_dense_grid *gr
   if (!e) return fail(DSR_E_ARG, "erase by mask: null engine");
   if (e->s.use_swapping) return fail(DSR_E_ARG, "erase by mask: engines with use_swapping are not supported");
   if (!grid || !mask) return fail(DSR_E_ARG, "erase by mask: null grid or mask");
-  if (grid->nx < 1 || grid->ny < 1 || grid->nz < 1) return fail(DSR_E_ARG, "erase by mask: a grid needs at least one point per axis");
-  long long n = (long long)grid->nx * grid->ny;
-  if (n > 2147483647ll || (n *= grid->nz) > 2147483647ll) return fail(DSR_E_ARG, "erase by mask: more than 2^31 - 1 grid points");
+  long long n = 0;
+  if (int st = grid_points_check(grid->nx, grid->ny, grid->nz, "erase by mask", &n)) return st;
   if (!std::isfinite(grid->pitch) || grid->pitch <= 0.0f) return fail(DSR_E_ARG, "erase by mask: pitch must be finite and positive");
   if (!rigid_transform(grid->grid_to_world_m)) return fail(DSR_E_ARG, "erase by mask: grid_to_world is not a rigid transform");
   dsr_erase_params prm;

@@ -5,15 +5,13 @@
 // engine forms.  Regular arrays only: no hash walk, no allocation in the engine, nothing of the engine is written.  Temporaries
 // (the packed 1-D distances, 4 bytes per point; the 2-D squared distances, 8 bytes per point) come from Scratch; the forms that
 // must not wait for their own work take them stream-ordered, so that their release does not wait either.
-#include "dsr_internal.h"
+#include "dsr_hostcall.h"
 using namespace dsr_internal;
 
 #include "k_esdf.h"
 #include "../../include/dsr_esdf.h"
 
 namespace {
-
-bool misaligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
 
 struct EsdfCall { EsdfP p; long long n; };
 constexpr int kEsdfMaxGrid = 16384, kEsdfMaxGridZ = 4096;  // workgroups of 4 waves
@@ -23,14 +21,6 @@ int esdf_check_params(const dsr_esdf_params *params, const char *what) {
   const std::string w(what);
   if (!params) return fail(DSR_E_ARG, w + ": null params");
   if (params->max_steps < 1 || params->max_steps > 2048) return fail(DSR_E_ARG, w + ": max_steps outside 1..2048");
-  return DSR_OK;
-}
-
-int esdf_check_shape(int32_t nx, int32_t ny, int32_t nz, const char *what, long long *n) {
-  const std::string w(what);
-  if (nx < 1 || ny < 1 || nz < 1) return fail(DSR_E_ARG, w + ": a grid needs at least one point per axis");
-  *n = (long long)nx * ny;
-  if (*n > 2147483647ll || (*n *= nz) > 2147483647ll) return fail(DSR_E_ARG, w + ": more than 2^31 - 1 grid points");
   return DSR_OK;
 }
 
@@ -50,16 +40,6 @@ void esdf_fill(EsdfCall &c, int32_t nx, int32_t ny, int32_t nz, float pitch, flo
   c.p.pitch = pitch; c.p.mu = mu;
 }
 
-template <class... Args, class... Params>
-void esdf_launch(dsr_engine *e, const char *name, hipStream_t stream, void (*kernel)(Params...), int grid, Args... args) {
-  if (e) {
-    ProfScope ps(e, name);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, stream, args...);
-  } else {
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, stream, args...);
-  }
-}
-
 // queue the transform on `stream` (device planes; counters may be null: nothing is counted); e: the engine whose stream it is (its
 // profile gets the launches), or null
 int esdf_queue(dsr_engine *e, hipStream_t stream, Scratch &sc, const EsdfCall &c, const float *sdf, const uint8_t *w, float *dist,
@@ -73,10 +53,10 @@ int esdf_queue(dsr_engine *e, hipStream_t stream, Scratch &sc, const EsdfCall &c
   // a wave per row / per tile of 64 x; beyond kEsdfMaxGrid workgroups the waves stride (tests/test_gpu_esdf.py has such a shape)
   const int gridX = (int)std::min<long long>((rows + 3) / 4, kEsdfMaxGrid), gridT = (int)std::min<long long>((tiles + 3) / 4, kEsdfMaxGrid);
   if (counters) HIP_TRY(hipMemsetAsync(counters, 0, EC_COUNT * sizeof *counters, stream));
-  esdf_launch(e, "esdf_x", stream, k_esdf_x, gridX, p, sdf, w, gx);
-  esdf_launch(e, "esdf_y", stream, k_esdf_y, gridT, p, (const uint32_t *)gx, gy);
+  launch_on(e, stream, "esdf_x", k_esdf_x, gridX, p, sdf, w, gx);
+  launch_on(e, stream, "esdf_y", k_esdf_y, gridT, p, (const uint32_t *)gx, gy);
   // (the last pass strides over the tiles with fewer workgroups — still more than are resident at once — so that few of them add to the counters)
-  esdf_launch(e, "esdf_z", stream, k_esdf_z, std::min(gridT, kEsdfMaxGridZ), p, sdf, w, (const uint32_t *)gx, (const int2 *)gy, dist, flags, d2o, d2i, counters);
+  launch_on(e, stream, "esdf_z", k_esdf_z, std::min(gridT, kEsdfMaxGridZ), p, sdf, w, (const uint32_t *)gx, (const int2 *)gy, dist, flags, d2o, d2i, counters);
   HIP_TRY(hipGetLastError());
   return DSR_OK;
 }
@@ -90,39 +70,28 @@ void esdf_fill_result(dsr_esdf_result *result, const unsigned long long *h) {
   result->far_points = (int64_t)h[EC_FAR];
 }
 
-// the transform with device planes on `stream`; result == null: queued only
-int esdf_run_dev(dsr_engine *e, hipStream_t stream, Scratch &sc, const EsdfCall &c, const float *sdf, const uint8_t *w, float *dist,
-                 uint8_t *flags, int32_t *d2o, int32_t *d2i, dsr_esdf_result *result) {
-  if (!result) return esdf_queue(e, stream, sc, c, sdf, w, dist, flags, d2o, d2i, nullptr);
-  unsigned long long *counters, h[EC_COUNT] = {};
-  if (int st = sc.get(&counters, EC_COUNT)) return st;
-  if (int st = esdf_queue(e, stream, sc, c, sdf, w, dist, flags, d2o, d2i, counters)) return st;
-  HIP_TRY(hipMemcpyAsync(h, counters, sizeof h, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));  // the one host wait
-  esdf_fill_result(result, h);
+// the transform with device planes on h's stream; result == null: queued only
+int esdf_run_dev(dsr_engine *e, HostCall &h, const EsdfCall &c, const float *sdf, const uint8_t *w, float *dist, uint8_t *flags,
+                 int32_t *d2o, int32_t *d2i, dsr_esdf_result *result) {
+  if (!result) return esdf_queue(e, h.stream, h.sc, c, sdf, w, dist, flags, d2o, d2i, nullptr);
+  unsigned long long hc[EC_COUNT] = {}, *counters = h.out(hc, EC_COUNT);
+  int st;
+  if ((st = h.begin()) || (st = esdf_queue(e, h.stream, h.sc, c, sdf, w, dist, flags, d2o, d2i, counters)) || (st = h.finish())) return st;
+  esdf_fill_result(result, hc);
   return DSR_OK;
 }
 
-// the transform with device inputs and HOST outputs on `stream`: staged outputs, the copies back, the one host wait
-int esdf_run_host_out(dsr_engine *e, hipStream_t stream, Scratch &sc, const EsdfCall &c, const float *sdf, const uint8_t *w, float *dist,
-                      uint8_t *flags, int32_t *d2o, int32_t *d2i, dsr_esdf_result *result) {
+// the transform with device inputs (or the staged ones of h) and HOST outputs: staged outputs, the copies back, the one host wait
+int esdf_run_host_out(dsr_engine *e, HostCall &h, const EsdfCall &c, const float *sdf, const uint8_t *w, float *dist, uint8_t *flags,
+                      int32_t *d2o, int32_t *d2i, dsr_esdf_result *result) {
   const size_t n = (size_t)c.n;
-  float *ddist = nullptr;
-  uint8_t *dflags = nullptr;
-  int32_t *dd2o = nullptr, *dd2i = nullptr;
-  unsigned long long *counters, h[EC_COUNT] = {};
+  float *ddist = h.out(dist, n);
+  uint8_t *dflags = h.out(flags, n);
+  int32_t *dd2o = h.out(d2o, n), *dd2i = h.out(d2i, n);
+  unsigned long long hc[EC_COUNT] = {}, *counters = h.out(hc, EC_COUNT);
   int st;
-  if ((dist && (st = sc.get(&ddist, n))) || (flags && (st = sc.get(&dflags, n))) || (d2o && (st = sc.get(&dd2o, n))) ||
-      (d2i && (st = sc.get(&dd2i, n))) || (st = sc.get(&counters, EC_COUNT)))
-    return st;
-  if ((st = esdf_queue(e, stream, sc, c, sdf, w, ddist, dflags, dd2o, dd2i, counters))) return st;
-  if (dist) HIP_TRY(hipMemcpyAsync(dist, ddist, n * sizeof(float), hipMemcpyDeviceToHost, stream));
-  if (flags) HIP_TRY(hipMemcpyAsync(flags, dflags, n, hipMemcpyDeviceToHost, stream));
-  if (d2o) HIP_TRY(hipMemcpyAsync(d2o, dd2o, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-  if (d2i) HIP_TRY(hipMemcpyAsync(d2i, dd2i, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(h, counters, sizeof h, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));  // the one host wait
-  if (result) esdf_fill_result(result, h);
+  if ((st = h.begin()) || (st = esdf_queue(e, h.stream, h.sc, c, sdf, w, ddist, dflags, dd2o, dd2i, counters)) || (st = h.finish())) return st;
+  if (result) esdf_fill_result(result, hc);
   return DSR_OK;
 }
 
@@ -130,7 +99,7 @@ int esdf_run_host_out(dsr_engine *e, hipStream_t stream, Scratch &sc, const Esdf
 int esdf_engine_setup(dsr_engine *e, const dsr_dense_grid *grid, const dsr_esdf_params *params, const char *what, long long *n) {
   if (int st = esdf_check_params(params, what)) return st;
   if (!e || !grid) return fail(DSR_E_ARG, std::string(what) + ": null argument");
-  return esdf_check_shape(grid->nx, grid->ny, grid->nz, what, n);
+  return grid_points_check(grid->nx, grid->ny, grid->nz, what, n);
 }
 
 // dsr_dense_export_dev into scratch planes (it refuses what dense_check refuses, before anything is queued), then the call's fields
@@ -167,21 +136,18 @@ int dsr_esdf_from_planes_dev(int device, void *hip_stream, int32_t nx, int32_t n
   EsdfCall c;
   if (int st = esdf_check_params(params, what)) return st;
   if (!sdf_dev) return fail(DSR_E_ARG, "esdf from planes: null sdf plane");
-  if (int st = esdf_check_shape(nx, ny, nz, what, &c.n)) return st;
+  if (int st = grid_points_check(nx, ny, nz, what, &c.n)) return st;
   if (int st = esdf_check_scale(pitch, mu, what)) return st;
-  if (misaligned4(sdf_dev) || misaligned4(dist_dev) || misaligned4(d2_out_dev) || misaligned4(d2_in_dev))
+  if (misaligned(sdf_dev, 4) || misaligned(dist_dev, 4) || misaligned(d2_out_dev, 4) || misaligned(d2_in_dev, 4))
     return fail(DSR_E_ARG, "esdf from planes: the float and int32 planes must be 4-byte aligned");
   const long long n = c.n;
   esdf_fill(c, nx, ny, nz, pitch, mu, params);
   c.n = n;
   HIP_TRY(hipSetDevice(device));
   hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  if (!result) {
-    Scratch sc("esdf: out of device memory for the temporaries", stream);  // stream-ordered: neither taken nor released with a wait
-    return esdf_run_dev(nullptr, stream, sc, c, sdf_dev, w_depth_dev, dist_dev, flags_dev, d2_out_dev, d2_in_dev, nullptr);
-  }
-  Scratch sc("esdf: out of device memory for the temporaries");
-  return esdf_run_dev(nullptr, stream, sc, c, sdf_dev, w_depth_dev, dist_dev, flags_dev, d2_out_dev, d2_in_dev, result);
+  Scratch sc("esdf: out of device memory for the temporaries", stream, !result);  // queued only: neither taken nor released with a wait
+  HostCall h(sc, stream);
+  return esdf_run_dev(nullptr, h, c, sdf_dev, w_depth_dev, dist_dev, flags_dev, d2_out_dev, d2_in_dev, result);
 }
 
 int dsr_esdf_from_planes(int device, void *hip_stream, int32_t nx, int32_t ny, int32_t nz, float pitch, float mu,
@@ -191,7 +157,7 @@ int dsr_esdf_from_planes(int device, void *hip_stream, int32_t nx, int32_t ny, i
   EsdfCall c;
   if (int st = esdf_check_params(params, what)) return st;
   if (!sdf) return fail(DSR_E_ARG, "esdf from planes: null sdf plane");
-  if (int st = esdf_check_shape(nx, ny, nz, what, &c.n)) return st;
+  if (int st = grid_points_check(nx, ny, nz, what, &c.n)) return st;
   if (int st = esdf_check_scale(pitch, mu, what)) return st;
   const size_t n = (size_t)c.n;
   esdf_fill(c, nx, ny, nz, pitch, mu, params);
@@ -199,33 +165,26 @@ int dsr_esdf_from_planes(int device, void *hip_stream, int32_t nx, int32_t ny, i
   HIP_TRY(hipSetDevice(device));
   hipStream_t stream = static_cast<hipStream_t>(hip_stream);
   Scratch sc("esdf: out of device memory for the staging buffers");
-  float *dsdf = nullptr;
-  uint8_t *dw = nullptr;
-  int st;
-  if ((st = sc.get(&dsdf, n)) || (w_depth && (st = sc.get(&dw, n)))) return st;
-  HIP_TRY(hipMemcpyAsync(dsdf, sdf, n * sizeof(float), hipMemcpyHostToDevice, stream));
-  if (w_depth) HIP_TRY(hipMemcpyAsync(dw, w_depth, n, hipMemcpyHostToDevice, stream));
-  return esdf_run_host_out(nullptr, stream, sc, c, dsdf, dw, dist, flags, d2_out, d2_in, result);
+  HostCall h(sc, stream);
+  const float *dsdf = h.in(sdf, n);
+  const uint8_t *dw = h.in(w_depth, n);
+  return esdf_run_host_out(nullptr, h, c, dsdf, dw, dist, flags, d2_out, d2_in, result);
 }
 
 int dsr_esdf_export_dev(dsr_engine *e, const dsr_dense_grid *grid, const dsr_esdf_params *params,
                         float *dist_dev, uint8_t *flags_dev, int32_t *d2_out_dev, int32_t *d2_in_dev, dsr_esdf_result *result) {
   long long n = 0;
   if (int st = esdf_engine_setup(e, grid, params, "esdf export", &n)) return st;
-  if (misaligned4(dist_dev) || misaligned4(d2_out_dev) || misaligned4(d2_in_dev))
+  if (misaligned(dist_dev, 4) || misaligned(d2_out_dev, 4) || misaligned(d2_in_dev, 4))
     return fail(DSR_E_ARG, "esdf export: the dist and d2 planes must be 4-byte aligned");
   CHECK_E_NOFLUSH(e);  // (the dense export below queues the deferred renders)
   EsdfCall c;
   float *sdf;
   uint8_t *w;
-  if (!result) {
-    Scratch sc("esdf export: out of device memory for the temporaries", e->stream);
-    if (int st = esdf_engine_export(e, grid, params, sc, n, c, &sdf, &w)) return st;
-    return esdf_run_dev(e, e->stream, sc, c, sdf, w, dist_dev, flags_dev, d2_out_dev, d2_in_dev, nullptr);
-  }
-  Scratch sc("esdf export: out of device memory for the temporaries");
+  Scratch sc("esdf export: out of device memory for the temporaries", e->stream, !result);
+  HostCall h(sc, e->stream);
   if (int st = esdf_engine_export(e, grid, params, sc, n, c, &sdf, &w)) return st;
-  return esdf_run_dev(e, e->stream, sc, c, sdf, w, dist_dev, flags_dev, d2_out_dev, d2_in_dev, result);
+  return esdf_run_dev(e, h, c, sdf, w, dist_dev, flags_dev, d2_out_dev, d2_in_dev, result);
 }
 
 int dsr_esdf_export(dsr_engine *e, const dsr_dense_grid *grid, const dsr_esdf_params *params,
@@ -237,8 +196,9 @@ int dsr_esdf_export(dsr_engine *e, const dsr_dense_grid *grid, const dsr_esdf_pa
   float *sdf;
   uint8_t *w;
   Scratch sc("esdf export: out of device memory for the staging buffers");
+  HostCall h(sc, e->stream);
   if (int st = esdf_engine_export(e, grid, params, sc, n, c, &sdf, &w)) return st;
-  return esdf_run_host_out(e, e->stream, sc, c, sdf, w, dist, flags, d2_out, d2_in, result);
+  return esdf_run_host_out(e, h, c, sdf, w, dist, flags, d2_out, d2_in, result);
 }
 
 }  // extern "C"

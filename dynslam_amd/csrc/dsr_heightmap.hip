@@ -3,7 +3,7 @@
 // One call = ONE launch of k_heightmap (k_heightmap.h) — preceded by a memset of the six counters only when a result is asked for —
 // on the engine's stream.  Everything the kernel needs travels as kernel arguments, so a _dev call that asks for no result
 // allocates nothing and waits for nothing.  Nothing of the engine is written.
-#include "dsr_internal.h"
+#include "dsr_hostcall.h"
 using namespace dsr_internal;
 
 #include "../../include/dsr_heightmap.h"
@@ -13,8 +13,6 @@ namespace {
 
 constexpr int kHeightMaxGrid = 16384;  // workgroups of 4 waves; beyond it the waves stride over the tiles (tests/test_gpu_heightmap.py
                                        // has such a launch through DSR_HEIGHTMAP_MAX_GRID)
-
-bool misaligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
 
 struct HeightCall { DenseP g; HeightP h; long long n2; };  // the checked arguments of one call
 
@@ -77,18 +75,18 @@ int dsr_heightmap_export_dev(dsr_engine *e, const dsr_dense_grid *grid, const ds
                              float *cost_dev, dsr_heightmap_result *result) {
   HeightCall c;
   if (int st = height_check(e, grid, params, c)) return st;
-  if (misaligned4(ground_dev) || misaligned4(top_dev) || misaligned4(ceiling_dev) || misaligned4(cost_dev) || misaligned4(rgba_dev))
+  if (misaligned(ground_dev, 4) || misaligned(top_dev, 4) || misaligned(ceiling_dev, 4) || misaligned(cost_dev, 4) || misaligned(rgba_dev, 4))
     return fail(DSR_E_ARG, "height map: the float and rgba planes must be 4-byte aligned");
   CHECK_E(e);
   HeightOut out{ground_dev, top_dev, ceiling_dev, cost_dev, reinterpret_cast<uint32_t *>(rgba_dev), flags_dev, n_up_dev, nullptr};
   if (!result) return height_queue(e, c, out);  // queued only: nothing allocated, no host wait
   Scratch sc("height map: out of device memory for the counters");
-  unsigned long long h[HC_COUNT] = {};
-  if (int st = sc.get(&out.counters, HC_COUNT)) return st;
-  if (int st = height_queue(e, c, out)) return st;
-  HIP_TRY(hipMemcpyAsync(h, out.counters, sizeof h, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));  // the one host wait
-  height_fill_result(result, h);
+  HostCall h(sc, e->stream);
+  unsigned long long hc[HC_COUNT] = {};
+  out.counters = h.out(hc, HC_COUNT);
+  int st;
+  if ((st = h.begin()) || (st = height_queue(e, c, out)) || (st = h.finish())) return st;
+  height_fill_result(result, hc);
   return DSR_OK;
 }
 
@@ -99,26 +97,16 @@ int dsr_heightmap_export(dsr_engine *e, const dsr_dense_grid *grid, const dsr_he
   CHECK_E(e);
   const size_t N = (size_t)c.n2;
   Scratch sc("height map: out of device memory for the staging buffers");
+  HostCall h(sc, e->stream);
+  unsigned long long hc[HC_COUNT] = {};
   HeightOut out{};
-  uint8_t *drgba = nullptr;
-  unsigned long long h[HC_COUNT] = {};
+  out.ground = h.out(ground, N); out.top = h.out(top, N); out.ceiling = h.out(ceiling, N);
+  out.rgba = reinterpret_cast<uint32_t *>(h.out(rgba, 4 * N));
+  out.flags = h.out(flags, N); out.nUp = h.out(n_up, N); out.cost = h.out(cost, N);
+  out.counters = h.out(hc, HC_COUNT);
   int st;
-  if ((ground && (st = sc.get(&out.ground, N))) || (top && (st = sc.get(&out.top, N))) || (ceiling && (st = sc.get(&out.ceiling, N))) ||
-      (rgba && (st = sc.get(&drgba, 4 * N))) || (flags && (st = sc.get(&out.flags, N))) || (n_up && (st = sc.get(&out.nUp, N))) ||
-      (cost && (st = sc.get(&out.cost, N))) || (st = sc.get(&out.counters, HC_COUNT)))
-    return st;
-  out.rgba = reinterpret_cast<uint32_t *>(drgba);
-  if ((st = height_queue(e, c, out))) return st;
-  if (ground) HIP_TRY(hipMemcpyAsync(ground, out.ground, N * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-  if (top) HIP_TRY(hipMemcpyAsync(top, out.top, N * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-  if (ceiling) HIP_TRY(hipMemcpyAsync(ceiling, out.ceiling, N * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-  if (rgba) HIP_TRY(hipMemcpyAsync(rgba, drgba, 4 * N, hipMemcpyDeviceToHost, e->stream));
-  if (flags) HIP_TRY(hipMemcpyAsync(flags, out.flags, N, hipMemcpyDeviceToHost, e->stream));
-  if (n_up) HIP_TRY(hipMemcpyAsync(n_up, out.nUp, N, hipMemcpyDeviceToHost, e->stream));
-  if (cost) HIP_TRY(hipMemcpyAsync(cost, out.cost, N * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(h, out.counters, sizeof h, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));  // the one host wait
-  if (result) height_fill_result(result, h);
+  if ((st = h.begin()) || (st = height_queue(e, c, out)) || (st = h.finish())) return st;
+  if (result) height_fill_result(result, hc);
   return DSR_OK;
 }
 

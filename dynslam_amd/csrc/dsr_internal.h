@@ -13,15 +13,19 @@
 //   dsr_align.hip     aligning one volume to another, SDF to SDF (include/dsr_align.h): the list of blocks, the queued evaluations
 //   dsr_mesh.hip      meshing (include/dsr.h, include/dsr_mesh.h): the soup mesh — resident, complete, coloured — and the indexed mesh;
 //                     their list step, plane pool and chunk loop, the read-backs, the OBJ / PLY writers, dsr_dump_merged_block
-//   dsr_esdf.hip      an exact Euclidean signed distance field from a dense grid (include/dsr_esdf.h): the checks, three launches
-//   dsr_query.hip     distance, gradient and colour of one or several volumes at arbitrary points (include/dsr_query.h): the checks,
-//                     the ordering of the engines' streams, the one launch
-//   dsr_heightmap.hip a bird's-eye height map of a volume over a dense grid's columns (include/dsr_heightmap.h): the checks, the one launch
+//   dsr_esdf.hip      an exact Euclidean signed distance field from a dense grid (include/dsr_esdf.h): three launches
+//   dsr_query.hip     distance, gradient and colour of one or several volumes at arbitrary points (include/dsr_query.h): the
+//                     ordering of the engines' streams, the one launch
+//   dsr_heightmap.hip a bird's-eye height map of a volume over a dense grid's columns (include/dsr_heightmap.h): the one launch
 //   dsr_erase.hip     erase and crop: a volume cleared by oriented boxes or by another volume's surface (include/dsr_erase.h): the checks,
 //                     the candidates, the one launch of k_erase.h, then the voxel GC's own commit and compaction; and the same by a
 //                     per-point mask on a dense grid (dsr_erase_by_mask of include/dsr_components.h)
-//   dsr_components.hip connected components of a dense grid and despeckle (include/dsr_components.h): the checks, the launches of
-//                     k_components.h around one scan, the read-back; dsr_despeckle = export, label, erase by mask
+//   dsr_components.hip connected components of a dense grid and despeckle (include/dsr_components.h): the launches of
+//                     k_components.h around one scan; dsr_despeckle = export, label, erase by mask
+// The units from dsr_merge.hip's dense grids down share their host-side scaffolding through dsr_hostcall.h (host code only: any unit
+// may include it): the alignment and grid-size checks, a launch under an optional profile label, and HostCall — the device twins
+// of a call's host planes, the uploads, the copies back with the counters among them, the ONE host wait.  Each unit keeps what
+// differs: its own checks and their order, its *_queue (the launches) and its *_fill_result (what the counters mean).
 // Every KERNEL header (k_*.h) is included by exactly ONE of them: __global__ kernels have external linkage.  Headers that hold only
 // inline device functions (dsr_device.h, dsr_math.h, dsr_sample.h, k_dense_sample.h) are shared: any unit may include them.
 #pragma once
@@ -409,6 +413,8 @@ struct Scratch {  // everything such a call allocates; freed when it leaves
   bool ordered = false;
   explicit Scratch(const char *what_) : what(what_) {}
   Scratch(const char *what_, hipStream_t stream_) : what(what_), stream(stream_), ordered(true) {}
+  // ... ordered only when asked: one body for a call that must not wait without a result and may with one
+  Scratch(const char *what_, hipStream_t stream_, bool ordered_) : what(what_), stream(stream_), ordered(ordered_) {}
   ~Scratch() { for (void *p : ptrs) (void)(ordered ? hipFreeAsync(p, stream) : hipFree(p)); }
   template <class T>
   int get(T **p, size_t n) {

@@ -11,7 +11,7 @@
 //   pull                  the write pass, in the same chunks;
 // then ONE host wait: the result words.  No count ever travels to the host in between: every pass is launched over the capacity of
 // the candidate arrays (src.sdf_local_block_num x the boxes per src block) and reads the live counts on the device.
-#include "dsr_internal.h"
+#include "dsr_hostcall.h"
 using namespace dsr_internal;
 #include <hipcub/hipcub.hpp>
 
@@ -198,9 +198,7 @@ int dsr_internal::dense_grid_check(dsr_engine *e, const dsr_dense_grid *grid, co
   const std::string w(what);
   if (!e || !grid) return fail(DSR_E_ARG, w + ": null argument");
   if (e->s.use_swapping) return fail(DSR_E_ARG, w + ": engines with use_swapping are not supported");
-  if (grid->nx < 1 || grid->ny < 1 || grid->nz < 1) return fail(DSR_E_ARG, w + ": a grid needs at least one point per axis");
-  n = (long long)grid->nx * grid->ny;
-  if (n > 2147483647ll || (n *= grid->nz) > 2147483647ll) return fail(DSR_E_ARG, w + ": more than 2^31 - 1 grid points");
+  if (int st = grid_points_check(grid->nx, grid->ny, grid->nz, what, &n)) return st;
   if (!std::isfinite(grid->pitch) || grid->pitch <= 0.0f) return fail(DSR_E_ARG, w + ": pitch must be finite and positive");
   if (std::isnan(grid->mu) || std::isinf(grid->mu)) return fail(DSR_E_ARG, w + ": mu is not finite");
   if (importFields && (grid->fill_w < 1 || grid->fill_w > 255)) return fail(DSR_E_ARG, w + ": fill_w outside 1..255");
@@ -232,13 +230,26 @@ int dense_check(dsr_engine *e, const dsr_dense_grid *grid, const char *what, Den
   return dsr_internal::dense_grid_check(e, grid, what, true, c.g, c.n);
 }
 
-bool misaligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
 // queue the export (device planes; count may be null)
 void dense_export_queue(dsr_engine *e, const DenseCall &c, float *sdf, uint8_t *wd, uint8_t *rgba, unsigned long long *count) {
   const long long tiles = (long long)div_up(c.g.nx, kDenseTileX) * div_up(c.g.ny, kDenseTileY) * div_up(c.g.nz, kDenseTileZ);
   const int grid = (int)std::min<long long>((tiles + 3) / 4, 32768);
   LAUNCH(e, "dense_export", k_dense_export, dim3(grid), dim3(256), c.g, e->scene, sdf, wd, reinterpret_cast<uint32_t *>(rgba), count);
+}
+
+// the export that counts, into device planes (the caller's, or the twins that h holds of its host planes): the one host wait
+int dense_export_run(dsr_engine *e, HostCall &h, const DenseCall &c, float *sdf, uint8_t *wd, uint8_t *rgba, dsr_dense_result *result) {
+  unsigned long long hcount = 0, *count = h.out(&hcount, 1);
+  if (int st = h.begin()) return st;
+  HIP_TRY(hipMemsetAsync(count, 0, sizeof *count, e->stream));
+  dense_export_queue(e, c, sdf, wd, rgba, count);
+  HIP_TRY(hipGetLastError());
+  if (int st = h.finish()) return st;
+  if (result) {
+    memset(result, 0, sizeof *result);
+    result->points_with_data = (int64_t)hcount;
+  }
+  return DSR_OK;
 }
 
 // the import's part of the parameters: the inverse transform and the candidate box; *N = the candidate blocks
@@ -334,16 +345,8 @@ int dsr_dense_export_dev(dsr_engine *e, const dsr_dense_grid *grid, float *sdf_d
     return DSR_OK;
   }
   Scratch sc("dense export: out of device memory");
-  unsigned long long *count, hcount = 0;
-  if (int st = sc.get(&count, 1)) return st;
-  HIP_TRY(hipMemsetAsync(count, 0, sizeof *count, e->stream));
-  dense_export_queue(e, c, sdf_dev, w_depth_dev, rgba_dev, count);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(&hcount, count, sizeof hcount, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  memset(result, 0, sizeof *result);
-  result->points_with_data = (int64_t)hcount;
-  return DSR_OK;
+  HostCall h(sc, e->stream);
+  return dense_export_run(e, h, c, sdf_dev, w_depth_dev, rgba_dev, result);
 }
 
 int dsr_dense_export(dsr_engine *e, const dsr_dense_grid *grid, float *sdf, uint8_t *w_depth, uint8_t *rgba, dsr_dense_result *result) {
@@ -352,26 +355,10 @@ int dsr_dense_export(dsr_engine *e, const dsr_dense_grid *grid, float *sdf, uint
   CHECK_E(e);
   Scratch sc("dense export: out of device memory for the staging buffers");
   const size_t n = (size_t)c.n;
-  float *dsdf = nullptr;
-  uint8_t *dw = nullptr, *drgba = nullptr;
-  unsigned long long *count, hcount = 0;
-  int st;
-  if ((sdf && (st = sc.get(&dsdf, n))) || (w_depth && (st = sc.get(&dw, n))) || (rgba && (st = sc.get(&drgba, 4 * n))) ||
-      (st = sc.get(&count, 1)))
-    return st;
-  HIP_TRY(hipMemsetAsync(count, 0, sizeof *count, e->stream));
-  dense_export_queue(e, c, dsdf, dw, drgba, count);
-  HIP_TRY(hipGetLastError());
-  if (sdf) HIP_TRY(hipMemcpyAsync(sdf, dsdf, n * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-  if (w_depth) HIP_TRY(hipMemcpyAsync(w_depth, dw, n, hipMemcpyDeviceToHost, e->stream));
-  if (rgba) HIP_TRY(hipMemcpyAsync(rgba, drgba, 4 * n, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(&hcount, count, sizeof hcount, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));  // the one host wait
-  if (result) {
-    memset(result, 0, sizeof *result);
-    result->points_with_data = (int64_t)hcount;
-  }
-  return DSR_OK;
+  HostCall h(sc, e->stream);
+  float *dsdf = h.out(sdf, n);
+  uint8_t *dw = h.out(w_depth, n), *drgba = h.out(rgba, 4 * n);
+  return dense_export_run(e, h, c, dsdf, dw, drgba, result);
 }
 
 int dsr_dense_import_dev(dsr_engine *e, const dsr_dense_grid *grid, const float *sdf_dev, const uint8_t *w_depth_dev,
@@ -396,14 +383,11 @@ int dsr_dense_import(dsr_engine *e, const dsr_dense_grid *grid, const float *sdf
   CHECK_E(e);
   Scratch sc("dense import: out of device memory for the staging buffers");
   const size_t n = (size_t)c.n;
-  float *dsdf = nullptr;
-  uint8_t *dw = nullptr, *drgba = nullptr;
-  int st;
-  if ((st = sc.get(&dsdf, n)) || (w_depth && (st = sc.get(&dw, n))) || (rgba && (st = sc.get(&drgba, 4 * n)))) return st;
-  HIP_TRY(hipMemcpyAsync(dsdf, sdf, n * sizeof(float), hipMemcpyHostToDevice, e->stream));
-  if (w_depth) HIP_TRY(hipMemcpyAsync(dw, w_depth, n, hipMemcpyHostToDevice, e->stream));
-  if (rgba) HIP_TRY(hipMemcpyAsync(drgba, rgba, 4 * n, hipMemcpyHostToDevice, e->stream));
-  return dense_import_run(e, c, N, dsdf, dw, drgba, result);
+  HostCall h(sc, e->stream);
+  const float *dsdf = h.in(sdf, n);
+  const uint8_t *dw = h.in(w_depth, n), *drgba = h.in(rgba, 4 * n);
+  if (int st = h.begin()) return st;
+  return dense_import_run(e, c, N, dsdf, dw, drgba, result);  // its own host wait: the staged planes are free afterwards
 }
 
 }  // extern "C"

@@ -4,7 +4,7 @@
 // One call = ONE launch of k_query_points (k_query.h) — preceded by a memset of the two counters only when a result is asked for —
 // on the stream of the (first) engine.  The per-volume constants travel as kernel arguments, so a call that asks for no result
 // allocates nothing and waits for nothing.  Nothing of an engine is written.
-#include "dsr_internal.h"
+#include "dsr_hostcall.h"
 using namespace dsr_internal;
 
 #include "../../include/dsr_query.h"
@@ -14,8 +14,6 @@ namespace {
 
 constexpr int kQueryMaxGrid = 16384;  // workgroups of 4 waves; beyond it the waves stride (tests/test_gpu_query.py has such a launch
                                       // through DSR_QUERY_MAX_GRID)
-
-bool misaligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
 
 // the checked arguments of one call
 struct QueryCall {
@@ -112,19 +110,18 @@ void query_fill_result(dsr_query_result *result, const unsigned long long *h) {
 
 // the _dev forms, after query_check
 int query_run_dev(QueryCall &c, bool multi, int32_t n, const float *points, QueryOut out, dsr_query_result *result, const char *what) {
-  if (misaligned4(points) || misaligned4(out.dist) || misaligned4(out.grad) || misaligned4(out.volume))
+  if (misaligned(points, 4) || misaligned(out.dist, 4) || misaligned(out.grad, 4) || misaligned(out.volume, 4))
     return fail(DSR_E_ARG, std::string(what) + ": the float and int32 planes must be 4-byte aligned");
   if (n == 0) { if (result) memset(result, 0, sizeof *result); return DSR_OK; }
   if (int st = query_enter(c)) return st;
   if (!result) return query_queue(c, multi, n, points, out);  // queued only: nothing allocated, no host wait
-  dsr_engine *e = c.engines[0];
   Scratch sc("query: out of device memory for the counters");
-  unsigned long long h[QC_COUNT] = {};
-  if (int st = sc.get(&out.counters, QC_COUNT)) return st;
-  if (int st = query_queue(c, multi, n, points, out)) return st;
-  HIP_TRY(hipMemcpyAsync(h, out.counters, sizeof h, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));  // the one host wait
-  query_fill_result(result, h);
+  HostCall h(sc, c.engines[0]->stream);
+  unsigned long long hc[QC_COUNT] = {};
+  out.counters = h.out(hc, QC_COUNT);
+  int st;
+  if ((st = h.begin()) || (st = query_queue(c, multi, n, points, out)) || (st = h.finish())) return st;
+  query_fill_result(result, hc);
   return DSR_OK;
 }
 
@@ -133,28 +130,16 @@ int query_run_host(QueryCall &c, bool multi, int32_t n, const float *points, flo
                    uint8_t *rgba, uint8_t *flags, dsr_query_result *result) {
   if (n == 0) { if (result) memset(result, 0, sizeof *result); return DSR_OK; }
   if (int st = query_enter(c)) return st;
-  dsr_engine *e = c.engines[0];
   const size_t N = (size_t)n;
   Scratch sc("query: out of device memory for the staging buffers");
-  float *dpoints = nullptr;
-  QueryOut out{};
-  unsigned long long h[QC_COUNT] = {};
+  HostCall h(sc, c.engines[0]->stream);
+  unsigned long long hc[QC_COUNT] = {};
+  const float *dpoints = h.in(points, 3 * N);
+  const QueryOut out{h.out(dist, N), h.out(grad, 3 * N), h.out(volume, N), h.out(wDepth, N), h.out(rgba, 4 * N), h.out(flags, N),
+                     h.out(hc, QC_COUNT)};  // (a braced list: evaluated left to right)
   int st;
-  if ((st = sc.get(&dpoints, 3 * N)) || (dist && (st = sc.get(&out.dist, N))) || (grad && (st = sc.get(&out.grad, 3 * N))) ||
-      (volume && (st = sc.get(&out.volume, N))) || (wDepth && (st = sc.get(&out.wDepth, N))) || (rgba && (st = sc.get(&out.rgba, 4 * N))) ||
-      (flags && (st = sc.get(&out.flags, N))) || (st = sc.get(&out.counters, QC_COUNT)))
-    return st;
-  HIP_TRY(hipMemcpyAsync(dpoints, points, 3 * N * sizeof(float), hipMemcpyHostToDevice, e->stream));
-  if ((st = query_queue(c, multi, n, dpoints, out))) return st;
-  if (dist) HIP_TRY(hipMemcpyAsync(dist, out.dist, N * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-  if (grad) HIP_TRY(hipMemcpyAsync(grad, out.grad, 3 * N * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-  if (volume) HIP_TRY(hipMemcpyAsync(volume, out.volume, N * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-  if (wDepth) HIP_TRY(hipMemcpyAsync(wDepth, out.wDepth, N, hipMemcpyDeviceToHost, e->stream));
-  if (rgba) HIP_TRY(hipMemcpyAsync(rgba, out.rgba, 4 * N, hipMemcpyDeviceToHost, e->stream));
-  if (flags) HIP_TRY(hipMemcpyAsync(flags, out.flags, N, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(h, out.counters, sizeof h, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));  // the one host wait
-  if (result) query_fill_result(result, h);
+  if ((st = h.begin()) || (st = query_queue(c, multi, n, dpoints, out)) || (st = h.finish())) return st;
+  if (result) query_fill_result(result, hc);
   return DSR_OK;
 }
 

@@ -57,6 +57,18 @@ def load_hip_api():
     return _hip_api
 
 
+def optional_api(api, key, missing=None):
+    """The entry points of the header that _capi.OPTIONAL_TABLES lists under `key`, bound once per `api` (what load_hip_api() or the
+    oracle's load_api() returned).  The ONE cache of such bindings: a dict on `api`, keyed by the table's name, so that no two tables
+    can share a slot.  A backend without the table: DsrError(DSR_E_ARG), in the caller's words (`missing`) where it has its own."""
+    cache = api.__dict__.setdefault("_optional", {})
+    if key not in cache:
+        cache[key] = _capi.bind_optional(api.lib, api.prefix, key)
+    if cache[key] is None:
+        raise DsrError(_capi.DSR_E_ARG, missing or f"this backend ({api.prefix}*) has {_capi.OPTIONAL_TABLES[key]['missing']}")
+    return cache[key]
+
+
 def default_settings(api=None, **overrides):
     api = api or load_hip_api()
     s = Settings()
@@ -338,12 +350,8 @@ class Batch:
         return list(self._status[:n]) if want_status else None
 
     def _track_api(self):
-        if not hasattr(self, "_tapi"):
-            self._tapi = _capi.bind_track(self.api.lib, self.api.prefix)
-        if self._tapi is None:
-            raise DsrError(_capi.DSR_E_ARG, f"this backend ({self.api.prefix}*) has no ICP tracker: dsr_batch_fuse_tracked is a "
-                                            "libdsr_hip.so entry point")
-        return self._tapi
+        return optional_api(self.api, "track", f"this backend ({self.api.prefix}*) has no ICP tracker: dsr_batch_fuse_tracked is a "
+                                               "libdsr_hip.so entry point")
 
     def fuse_tracked(self, items, settings=None, want_status=False):
         """`fuse` with the reference's ITM refinement (enable_itm_refinement_, InstanceReconstructor.cpp:590-650): every volume
@@ -366,12 +374,8 @@ class Batch:
         return (out, list(self._status[:n])) if want_status else out
 
     def _gc_api(self):
-        if not hasattr(self, "_gapi"):
-            self._gapi = _capi.bind_gc(self.api.lib, self.api.prefix)
-        if self._gapi is None:
-            raise DsrError(_capi.DSR_E_ARG, f"this backend ({self.api.prefix}*) has no batch GC: dsr_batch_decay is a "
+        return optional_api(self.api, "gc", f"this backend ({self.api.prefix}*) has no batch GC: dsr_batch_decay is a "
                                             "libdsr_hip.so entry point")
-        return self._gapi
 
     def decay(self, items):
         """The voxel GC of the listed volumes in the same launches (dsr_batch_decay, include/dsr_gc.h): per item, in order, what
@@ -539,11 +543,7 @@ class EngineCore:
 
     # -- tracking (include/dsr_track.h) ---------------------------------------
     def _track_api(self):
-        if not hasattr(self, "_tapi"):
-            self._tapi = _capi.bind_track(self.api.lib, self.api.prefix)
-        if self._tapi is None:
-            raise DsrError(_capi.DSR_E_ARG, f"this backend ({self.api.prefix}*) has no ICP tracker: dsr_track is a libdsr_hip.so entry point")
-        return self._tapi
+        return optional_api(self.api, "track")
 
     def track_default_settings(self):
         s = _capi.TrackSettings()
@@ -605,11 +605,7 @@ class EngineCore:
         self._check(self.api.decay(self._h, int(max_weight), int(min_age), int(bool(force_all_voxels))))
 
     def _gc_api(self):
-        if not hasattr(self, "_gapi"):
-            self._gapi = _capi.bind_gc(self.api.lib, self.api.prefix)
-        if self._gapi is None:
-            raise DsrError(_capi.DSR_E_ARG, f"this backend ({self.api.prefix}*) has no include/dsr_gc.h entry points")
-        return self._gapi
+        return optional_api(self.api, "gc")
 
     def debug_alloc_list(self):
         """For tests (dsr_gc_debug_alloc_list): -> (valid, ids) — the sorted list of allocated entries of an instance-sized volume
@@ -628,11 +624,7 @@ class EngineCore:
 
     # -- snapshots (include/dsr_snapshot.h) ----------------------------------
     def _snapshot_api(self):
-        if not hasattr(self, "_sapi"):
-            self._sapi = _capi.bind_snapshot(self.api.lib, self.api.prefix)
-        if self._sapi is None:
-            raise DsrError(_capi.DSR_E_ARG, f"this backend ({self.api.prefix}*) has no include/dsr_snapshot.h entry points")
-        return self._sapi
+        return optional_api(self.api, "snapshot")
 
     def save_snapshot(self, path):
         """The engine's complete state into a file (dsr_snapshot_save); reads only."""
@@ -760,11 +752,7 @@ class EngineCore:
 
     # ---- the complete mesh of a swapping engine (include/dsr_mesh.h; builder-defined)
     def _mesh_api(self):
-        if not hasattr(self, "_mapi"):
-            self._mapi = _capi.bind_mesh(self.api.lib, self.api.prefix)
-        if self._mapi is None:
-            raise DsrError(_capi.DSR_E_ARG, f"this backend ({self.api.prefix}*) has no include/dsr_mesh.h entry points")
-        return self._mapi
+        return optional_api(self.api, "mesh")
 
     def mesh_scene_complete(self):
         """mesh_scene over every entry that owns voxel data, the blocks in the host store included (dsr_mesh_scene_complete);
@@ -864,11 +852,7 @@ class EngineCore:
 
     # ---- folding another volume into this one (include/dsr_merge.h; builder-defined)
     def _merge_api(self):
-        if not hasattr(self, "_mergeapi"):   # (an attribute of its own: `_gapi` is the voxel GC's)
-            self._mergeapi = _capi.bind_merge(self.api.lib, self.api.prefix)
-        if self._mergeapi is None:
-            raise DsrError(_capi.DSR_E_ARG, f"this backend ({self.api.prefix}*) has no include/dsr_merge.h entry points")
-        return self._mergeapi
+        return optional_api(self.api, "merge")
 
     def merge_from(self, src, src_to_dst, min_w_depth=1, merge_colour=True):
         """Resample the volume of engine `src` into this one (dsr_merge_volume); src_to_dst: 4x4, metres of src's world -> metres
@@ -890,11 +874,7 @@ class EngineCore:
 
     # ---- erase and crop (include/dsr_erase.h; builder-defined)
     def _erase_api(self):
-        if not hasattr(self, "_eapi"):
-            self._eapi = _capi.bind_erase(self.api.lib, self.api.prefix)
-        if self._eapi is None:
-            raise DsrError(_capi.DSR_E_ARG, f"this backend ({self.api.prefix}*) has no include/dsr_erase.h entry points")
-        return self._eapi
+        return optional_api(self.api, "erase")
 
     def _erase_params(self, mode, free_blocks, min_w_depth=1, margin=0.0):
         modes = {"inside": _capi.ERASE_INSIDE, "outside": _capi.ERASE_OUTSIDE}
@@ -936,11 +916,7 @@ class EngineCore:
 
     # ---- connected components, erase by mask, despeckle (include/dsr_components.h; builder-defined)
     def _comp_api(self):
-        if not hasattr(self, "_compapi"):
-            self._compapi = _capi.bind_components(self.api.lib, self.api.prefix)
-        if self._compapi is None:
-            raise DsrError(_capi.DSR_E_ARG, f"this backend ({self.api.prefix}*) has no include/dsr_components.h entry points")
-        return self._compapi
+        return optional_api(self.api, "components")
 
     def components(self, shape, pitch, grid_to_world=None, *, connectivity=6, threshold=0.0, min_points=0, keep_border=True,
                    capacity=4096, mu=None, sampling="nearest", min_w_depth=1, labels=True, mask=False, torch_out=False):
@@ -1058,11 +1034,7 @@ class EngineCore:
 
     # ---- the volume as a dense grid and back (include/dsr_dense.h; builder-defined)
     def _dense_api(self):
-        if not hasattr(self, "_dapi"):
-            self._dapi = _capi.bind_dense(self.api.lib, self.api.prefix)
-        if self._dapi is None:
-            raise DsrError(_capi.DSR_E_ARG, f"this backend ({self.api.prefix}*) has no include/dsr_dense.h entry points")
-        return self._dapi
+        return optional_api(self.api, "dense")
 
     def _torch_device(self):
         """the engine's GPU as a torch.device (settings.device -1: the device that was current at creation, taken to be current still)"""
@@ -1168,11 +1140,7 @@ class EngineCore:
 
     # ---- the volume's Euclidean signed distance field on a dense grid (include/dsr_esdf.h; builder-defined)
     def _esdf_api(self):
-        if not hasattr(self, "_esdfapi"):   # (an attribute of its own: `_eapi` is the erase's)
-            self._esdfapi = _capi.bind_esdf(self.api.lib, self.api.prefix)
-        if self._esdfapi is None:
-            raise DsrError(_capi.DSR_E_ARG, f"this backend ({self.api.prefix}*) has no include/dsr_esdf.h entry points")
-        return self._esdfapi
+        return optional_api(self.api, "esdf")
 
     def to_esdf(self, shape, pitch, grid_to_world=None, *, max_distance=None, max_steps=32, mu=None, sampling="trilinear", min_w_depth=1,
                 keep_tsdf=True, planes=("dist", "flags"), torch_out=False):
@@ -1218,11 +1186,7 @@ class EngineCore:
 
     # ---- a bird's-eye height map over a dense grid's columns (include/dsr_heightmap.h; builder-defined)
     def _heightmap_api(self):
-        if not hasattr(self, "_hapi"):
-            self._hapi = _capi.bind_heightmap(self.api.lib, self.api.prefix)
-        if self._hapi is None:
-            raise DsrError(_capi.DSR_E_ARG, f"this backend ({self.api.prefix}*) has no include/dsr_heightmap.h entry points")
-        return self._hapi
+        return optional_api(self.api, "heightmap")
 
     def to_heightmap(self, shape, pitch, grid_to_world=None, mu=None, sampling="trilinear", min_w_depth=1, band=(0.2, 2.0),
                      planes=HEIGHTMAP_PLANES, out=None, torch_out=False):
@@ -1276,11 +1240,7 @@ class EngineCore:
 
     # ---- aligning another volume to this one (include/dsr_align.h; builder-defined)
     def _align_api(self):
-        if not hasattr(self, "_aapi"):
-            self._aapi = _capi.bind_align(self.api.lib, self.api.prefix)
-        if self._aapi is None:
-            raise DsrError(_capi.DSR_E_ARG, f"this backend ({self.api.prefix}*) has no include/dsr_align.h entry points")
-        return self._aapi
+        return optional_api(self.api, "align")
 
     def align_from(self, src, init_src_to_dst, log_capacity=None, **params):
         """Refine init_src_to_dst (4x4, metres of src's world -> metres of this engine's world, row-major numpy) by SDF-to-SDF
@@ -1358,9 +1318,7 @@ class Snapshot:
 def snapshot_info(path, api=None):
     """Settings, image size, blocks in use, bytes and sections of a snapshot file (dsr_snapshot_info) -> _capi.SnapshotInfo."""
     api = api or load_hip_api()
-    sapi = _capi.bind_snapshot(api.lib, api.prefix)
-    if sapi is None:
-        raise DsrError(_capi.DSR_E_ARG, f"this backend ({api.prefix}*) has no include/dsr_snapshot.h entry points")
+    sapi = optional_api(api, "snapshot")
     out = _capi.SnapshotInfo()
     st = sapi.snapshot_info(str(path).encode(), None, C.byref(out))
     if st != DSR_OK:

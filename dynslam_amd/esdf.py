@@ -7,25 +7,16 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from .engine import (ESDF_PLANES, DsrError, _esdf_plane_names, _ptr, esdf_params, esdf_result_dict, load_hip_api)
-
-_api = None
+from .engine import (ESDF_PLANES, DsrError, _esdf_plane_names, _ptr, esdf_params, esdf_result_dict, load_hip_api, optional_api)
 
 
 def _esdf_api():
-    global _api
-    if _api is None:
-        hip = load_hip_api()
-        _api = _capi.bind_esdf(hip.lib, hip.prefix)
-        if _api is None:
-            raise DsrError(_capi.DSR_E_ARG, "libdsr_hip.so has no include/dsr_esdf.h entry points")
-        _api.last_error = hip.last_error
-    return _api
+    return optional_api(load_hip_api(), "esdf", "libdsr_hip.so has no include/dsr_esdf.h entry points")
 
 
-def _check(api, status):
+def _check(status):
     if status != _capi.DSR_OK:
-        msg = api.last_error()
+        msg = load_hip_api().last_error()
         raise DsrError(status, msg.decode() if msg else "")
 
 
@@ -55,9 +46,9 @@ def esdf_from_planes(sdf, w_depth=None, *, pitch, mu, max_distance=None, max_ste
             out = {k: torch.empty(shape, dtype=getattr(torch, ESDF_PLANES[k]), device=sdf.device) for k in names}
             stream = torch.cuda.current_stream(sdf.device).cuda_stream
             ptrs = [out[k].data_ptr() if k in out else None for k in ESDF_PLANES]
-            _check(api, api.esdf_from_planes_dev(sdf.device.index, C.c_void_p(stream), nx, ny, nz, float(pitch), float(mu), sdf.data_ptr(),
-                                                 None if w_depth is None else w_depth.data_ptr(), C.byref(p), *ptrs,
-                                                 C.byref(res) if wait else None))
+            _check(api.esdf_from_planes_dev(sdf.device.index, C.c_void_p(stream), nx, ny, nz, float(pitch), float(mu), sdf.data_ptr(),
+                                            None if w_depth is None else w_depth.data_ptr(), C.byref(p), *ptrs,
+                                            C.byref(res) if wait else None))
         if not wait:
             return out
     else:
@@ -69,7 +60,7 @@ def esdf_from_planes(sdf, w_depth=None, *, pitch, mu, max_distance=None, max_ste
             raise DsrError(_capi.DSR_E_ARG, f"esdf_from_planes: a weight plane of shape {w_depth.shape}, expected {shape}")
         out = {k: np.empty(shape, ESDF_PLANES[k]) for k in names}
         ptrs = [_ptr(out[k]) if k in out else None for k in ESDF_PLANES]
-        _check(api, api.esdf_from_planes(int(device), None, nx, ny, nz, float(pitch), float(mu), _ptr(sdf),
-                                         None if w_depth is None else _ptr(w_depth), C.byref(p), *ptrs, C.byref(res)))
+        _check(api.esdf_from_planes(int(device), None, nx, ny, nz, float(pitch), float(mu), _ptr(sdf),
+                                    None if w_depth is None else _ptr(w_depth), C.byref(p), *ptrs, C.byref(res)))
     out.update(esdf_result_dict(res))
     return out

@@ -6,15 +6,11 @@ static and dynamic DepthFrameEvaluation records, count for count the reference's
 lines its CsvWriter writes (Records.h).
 """
 import ctypes as C
-import os
 from dataclasses import dataclass, field
 
 import numpy as np
 
 from . import _capi
-
-_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libdsr_hip.so")
-_API = None
 
 # EvaluateFrameSeparate (Evaluation.cpp:112-129): delta 0.5, 1 .. 12, then KITTI-style 3 (delta AND > 5 % of the LIDAR disparity)
 REFERENCE_CONFIGS = tuple([(0.5, False)] + [(float(d), False) for d in range(1, 13)] + [(3.0, True)])
@@ -23,22 +19,13 @@ STATIC, DYNAMIC, SKIP = _capi.EVAL_STATIC, _capi.EVAL_DYNAMIC, _capi.EVAL_SKIP
 
 
 def _api():
-    global _API
-    if _API is None:
-        _capi.preload_hip_runtime()
-        lib = C.CDLL(_LIB)
-        api = _capi.bind_eval(lib, "dsr_")
-        if api is None:
-            raise ImportError(f"{_LIB} has no LIDAR evaluator (include/dsr_eval.h)")
-        api.lib = lib
-        _API = api
-    return _API
+    from .engine import load_hip_api, optional_api
+    return optional_api(load_hip_api(), "eval")
 
 
 def _last_error():
-    f = _api().lib.dsr_last_error
-    f.restype = C.c_char_p
-    return f().decode(errors="replace")
+    from .engine import load_hip_api
+    return (load_hip_api().last_error() or b"").decode(errors="replace")
 
 
 def read_velodyne(path):

@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from .engine import DsrError, _colmajor, _ptr
+from .engine import DsrError, _colmajor, _ptr, optional_api
 
 # the output planes in the order of the entry points: name -> (element type, trailing shape)
 PLANES = {"dist": ("float32", ()), "grad": ("float32", (3,)), "volume": ("int32", ()), "w_depth": ("uint8", ()), "rgba": ("uint8", (4,)),
@@ -16,11 +16,7 @@ SAMPLING = {"nearest": _capi.QUERY_NEAREST, "trilinear": _capi.QUERY_TRILINEAR}
 
 
 def query_api(core):
-    if not hasattr(core, "_qapi"):
-        core._qapi = _capi.bind_query(core.api.lib, core.api.prefix)
-    if core._qapi is None:
-        raise DsrError(_capi.DSR_E_ARG, f"this backend ({core.api.prefix}*) has no include/dsr_query.h entry points")
-    return core._qapi
+    return optional_api(core.api, "query")
 
 
 def query_params(api, pose=None, sampling="trilinear", min_w_depth=1, out=None):

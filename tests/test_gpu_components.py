@@ -140,6 +140,39 @@ def test_table_properties_from_numpy(hip_api, connectivity):
         assert np.all(np.diff(t["root"]) > 0)
 
 
+def test_host_form_with_one_output_at_a_time(hip_api):
+    """dsr_components_from_planes with ONE of labels, table and mask, the others NULL, on 17 x 5 x 5 points (one more than 16 x 4 x 4
+    per axis): what it stages and copies back is the output asked for, byte for byte that of the call with all three — which is the
+    restatement's —, the table's records past components_written are not the caller's to see, and buffers that were not handed over
+    keep their pattern"""
+    from dynslam_amd.components import _comp_api
+    api = _comp_api()
+    occ = cu.random_occ((17, 5, 5), 0.3, 3)
+    st, want, want_counts = cu.ref_components(occ=occ, connectivity=6, min_points=3, capacity=CAPACITY)
+    assert st == 0 and 2 <= want_counts["components"] < CAPACITY and want_counts["small_components"] >= 1
+    p = _capi.CompParams()
+    api.components_default_params(C.byref(p))
+    p.connectivity, p.min_points = 6, 3
+
+    def call(outputs):
+        bufs = dict(labels=np.full(occ.shape, 77, np.int32), table=np.full(CAPACITY * 64, 77, np.uint8), mask=np.full(occ.shape, 77, np.uint8))
+        res = _capi.CompResult()
+        ptrs = {k: bufs[k].ctypes.data if k in outputs else None for k in OUTPUTS}
+        assert api.components_from_planes(0, None, 17, 5, 5, None, None, occ.ctypes.data, C.byref(p), ptrs["labels"], ptrs["table"], CAPACITY,
+                                          ptrs["mask"], C.byref(res)) == _capi.DSR_OK
+        assert all((bufs[k] == 77).all() for k in OUTPUTS if k not in outputs), "a buffer that was not handed over has changed"
+        return bufs, {k: int(getattr(res, k)) for k in cu.RESULT_KEYS}
+
+    whole, counts = call(OUTPUTS)
+    written = 64 * want_counts["components_written"]
+    assert counts == want_counts and cu.same_bytes(whole["labels"], want["labels"]) and cu.same_bytes(whole["mask"], want["mask"])
+    assert whole["table"][:written].tobytes() == want["table"].tobytes() and (whole["table"][written:] == 77).all()
+    for only in OUTPUTS:
+        got, c = call((only,))
+        assert c == dict(want_counts, components_written=want_counts["components_written"] if only == "table" else 0), only
+        assert got[only].tobytes() == whole[only].tobytes(), only
+
+
 def test_labelling_refusals(hip_api):
     import torch
     occ = cu.random_occ((37, 21, 13), 0.25, 1)

@@ -64,8 +64,9 @@ def _export_raw(e, g, planes, dev, with_result=True):
     """dsr_dense_export / _dev with exactly the planes named, the others NULL -> (dict of numpy planes, points_with_data or None);
     absent planes' poison must survive"""
     import torch
-    grid = e._dense_grid(g["shape"][::-1], g["pitch"], g["grid_to_world"], g["mu"], g["sampling"], g["min_w_depth"])
-    shapes = dict(sdf=(NP_SHAPE, np.float32), w_depth=(NP_SHAPE, np.uint8), rgba=(NP_SHAPE + (4,), np.uint8))
+    np_shape = g["shape"][::-1]
+    grid = e._dense_grid(np_shape, g["pitch"], g["grid_to_world"], g["mu"], g["sampling"], g["min_w_depth"])
+    shapes = dict(sdf=(np_shape, np.float32), w_depth=(np_shape, np.uint8), rgba=(np_shape + (4,), np.uint8))
     res = _capi.DenseResult()
     rp = C.byref(res) if with_result else None
     if dev:
@@ -76,8 +77,10 @@ def _export_raw(e, g, planes, dev, with_result=True):
             e.stream_wait_for_engine(torch.cuda.current_stream().cuda_stream)
         out = {k: v.cpu().numpy() for k, v in bufs.items()}
     else:
-        out = {k: np.full(shapes[k][0], 77, shapes[k][1]) for k in planes}
-        e._check(e._dense_api().dense_export(e._h, C.byref(grid), *(out[k].ctypes.data if k in out else None for k in shapes), rp))
+        bufs = {k: np.full(shapes[k][0], 77, shapes[k][1]) for k in shapes}
+        e._check(e._dense_api().dense_export(e._h, C.byref(grid), *(bufs[k].ctypes.data if k in planes else None for k in shapes), rp))
+        assert all((bufs[k] == 77).all() for k in shapes if k not in planes), "a plane that was not handed over has changed"
+        out = {k: bufs[k] for k in planes}
     return out, (int(res.points_with_data) if with_result else None)
 
 
@@ -127,6 +130,15 @@ def test_rigid_export_equals_the_reference(fine, sampling):
     got, n = _export_raw(e, g, ("sdf", "w_depth", "rgba"), True, with_result=False)
     assert n is None
     _assert_planes_equal(got, want, "queued _dev form")
+    # the host form with ONE plane at a time, on a grid one point larger than a tile per axis: what it stages and copies back is the
+    # plane asked for, byte for byte that of the call with all three
+    small = tuple(t + 1 for t in TILE)
+    gs = du.grid_spec(small, PITCH, du.place_rigid(fine["state"], mu.FINE, small, PITCH), sampling=sampling)
+    whole, n_whole = _export_raw(e, gs, ("sdf", "w_depth", "rgba"), False)
+    assert 0 < n_whole < np.prod(small) and n_whole == int((whole["w_depth"] > 0).sum())
+    for only in ("sdf", "w_depth", "rgba"):
+        got, n = _export_raw(e, gs, (only,), False)
+        assert n == n_whole and set(got) == {only} and _same_bytes(got[only], whole[only]), only
     # another unit for the values
     scaled = e.to_dense(NP_SHAPE, PITCH, fine["T"], mu=0.3, sampling=sampling, colour=False)
     want3, _ = du.ref_export(fine["state"], mu.FINE, _grid(fine, sampling=sampling, mu=0.3), planes=("sdf", "w_depth"))

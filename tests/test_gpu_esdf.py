@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from dynslam_amd import _capi
-from dynslam_amd.engine import DsrError, EngineCore, InfiniTamDriver, default_settings, esdf_params
+from dynslam_amd.engine import DsrError, EngineCore, InfiniTamDriver, default_settings, esdf_params, load_hip_api
 from dynslam_amd.esdf import _esdf_api, esdf_from_planes
 from tests import dense_util as du
 from tests import esdf_util as eu
@@ -47,14 +47,16 @@ def _raw(sdf, w, planes=ALL, dev=False, with_result=True, pitch=PITCH, mu_=MU, *
             bufs = {k: torch.full(sdf.shape, POISON, dtype=getattr(torch, TORCH[k]), device="cuda") for k in planes}
             st = api.esdf_from_planes_dev(0, C.c_void_p(side.cuda_stream), nx, ny, nz, pitch, mu_, tsdf.data_ptr(),
                                           None if tw is None else tw.data_ptr(), C.byref(p), *(bufs[k].data_ptr() if k in bufs else None for k in ALL), rp)
-            assert st == _capi.DSR_OK, api.last_error()
+            assert st == _capi.DSR_OK, load_hip_api().last_error()
             out = {k: v.cpu().numpy() for k, v in bufs.items()}   # (queued form: the copy is ordered behind the call's work by the stream)
         side.synchronize()
     else:
-        out = {k: np.full(sdf.shape, POISON, eu.PLANES[k]) for k in planes}
+        bufs = {k: np.full(sdf.shape, POISON, eu.PLANES[k]) for k in ALL}
         st = api.esdf_from_planes(0, None, nx, ny, nz, pitch, mu_, sdf.ctypes.data, None if w is None else w.ctypes.data, C.byref(p),
-                                  *(out[k].ctypes.data if k in out else None for k in ALL), rp)
-        assert st == _capi.DSR_OK, api.last_error()
+                                  *(bufs[k].ctypes.data if k in planes else None for k in ALL), rp)
+        assert st == _capi.DSR_OK, load_hip_api().last_error()
+        assert all((bufs[k] == POISON).all() for k in ALL if k not in planes), "a plane that was not handed over has changed"
+        out = {k: bufs[k] for k in planes}
     return out, ({k: int(getattr(res, k)) for k in eu.RESULT_KEYS} if with_result else None)
 
 
@@ -185,6 +187,17 @@ def test_absent_planes_and_the_queued_form(field):
     _assert_equal(got, want, "queued _dev form")
     got, c = _raw(sdf, w, ("dist",), True, with_result=False, **params)
     _assert_equal(got, want, "queued _dev form, one plane", ("dist",))
+    # the host form with ONE plane at a time, 17 x 5 x 5 points: the plane asked for, byte for byte that of the call with all four
+    sdf, w = eu.random_field((17, 5, 5), 12)
+    want, counts = eu.ref_esdf(sdf, w, pitch=PITCH, mu=MU, **params)
+    assert counts["outside_sites"] > 50 and counts["inside_sites"] > 50 and 0 < counts["points_with_data"] < sdf.size
+    whole, c = _raw(sdf, w, ALL, False, **params)
+    assert c == counts
+    _assert_equal(whole, want, "17 x 5 x 5, every plane")
+    for only in ALL:
+        got, c = _raw(sdf, w, (only,), False, **params)
+        assert c == counts and set(got) == {only}
+        _assert_equal(got, whole, f"17 x 5 x 5, {only} alone", (only,))
 
 
 # 5. the engine path
