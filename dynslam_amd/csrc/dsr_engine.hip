@@ -1024,7 +1024,8 @@ static int render_common(dsr_engine *e, int type, const float pose_m[16], const 
       if (rgba_out) {
         int st = before_fusion(e);
         if (st) return st;
-        HIP_TRY(hipMemcpyAsync(rgba_out, e->rgb, P * 4, kind, e->stream));
+        // the colour frame has the COLOUR camera's size (e->rgb holds Wr * Hr pixels)
+        HIP_TRY(hipMemcpyAsync(rgba_out, e->rgb, (size_t)e->Wr * e->Hr * 4, kind, e->stream));
         if ((st = after_fusion(e))) return st;
       }
       break;

@@ -548,7 +548,8 @@ static int extract_silhouette(dsr_engine *main_engine, dsr_engine *instance, con
   if (blank && ((!rmask && !rmaskDev) || rbw <= 0 || rbh <= 0)) return fail(DSR_E_ARG, "bad silhouette arguments");
   if (!main_engine->hasView) return fail(DSR_E_NO_VIEW, "no view yet");
   if (instance->W != main_engine->W || instance->H != main_engine->H ||
-      instance->Wr != main_engine->Wr || instance->Hr != main_engine->Hr || main_engine->W != main_engine->Wr)
+      instance->Wr != main_engine->Wr || instance->Hr != main_engine->Hr || main_engine->W != main_engine->Wr ||
+      main_engine->H != main_engine->Hr)  // (the kernels index the colour frame with the depth frame's W and H)
     return fail(DSR_E_ARG, "main and instance engines must share the image size");
   int maskSlot = -1, rmaskSlot = -1;
   if (!maskDev && blank && !rmaskDev) {  // two host masks for one kernel: the ring must hold the larger one before the first is staged

@@ -94,6 +94,30 @@ def make_calib(fx, fy, cx, cy, width, height):
     return c
 
 
+def make_calib_rgbd(depth, rgb, trafo_rgb_to_depth=None):
+    """A calib whose colour camera differs from the depth camera (ITMRGBDCalib in general): `depth` and `rgb` are
+    (fx, fy, cx, cy, width, height), `trafo_rgb_to_depth` a 4x4 math matrix (None: identity) — the extrinsic whose INVERSE
+    takes depth-camera coordinates to colour-camera coordinates (M_rgb = inv(trafo) * M_d)."""
+    c = make_calib(*depth)
+    c.rgb.fx, c.rgb.fy, c.rgb.cx, c.rgb.cy = (float(v) for v in rgb[:4])
+    c.rgb.width, c.rgb.height = int(rgb[4]), int(rgb[5])
+    if trafo_rgb_to_depth is not None:
+        c.trafo_rgb_to_depth[:] = _colmajor(trafo_rgb_to_depth).tolist()
+    return c
+
+
+def calib_same_size(calib):
+    return calib.rgb.width == calib.depth.width and calib.rgb.height == calib.depth.height
+
+
+def require_same_size(calib, who):
+    """The callers above the engine that move whole frames between the colour and the depth image (silhouette split, previews,
+    the volume batch) need both of one size; they say so up front instead of passing the calib through."""
+    if not calib_same_size(calib):
+        raise DsrError(_capi.DSR_E_ARG, f"{who} needs colour and depth images of one size, got colour {calib.rgb.width}x{calib.rgb.height}"
+                                        f" and depth {calib.depth.width}x{calib.depth.height}")
+
+
 def _colmajor(m):
     """4x4 math matrix -> float[16] column-major (ORUtils::Matrix4f::m)."""
     a = np.ascontiguousarray(np.asarray(m, dtype=np.float32).reshape(4, 4).T).reshape(-1)
@@ -300,6 +324,8 @@ class Batch:
     def __init__(self, source, volumes, api=None):
         self.api = api or source.api
         self.source, self.volumes = source, list(volumes)
+        for eng in [source] + self.volumes:
+            require_same_size(eng.calib, "a volume batch")
         arr = (C.c_void_p * len(self.volumes))(*[v._h for v in self.volumes])
         h = C.c_void_p()
         self._check(self.api.batch_create(source._h, arr, len(self.volumes), C.byref(h)))
@@ -410,6 +436,7 @@ class EngineCore:
         self.settings = settings
         self.calib = calib
         self.W, self.H = calib.depth.width, calib.depth.height
+        self.Wr, self.Hr = calib.rgb.width, calib.rgb.height  # the colour camera's image (== W, H in DynSLAM)
         self.no_total_entries = settings.hash_bucket_num + settings.excess_list_size
         self.no_blocks = settings.sdf_local_block_num
         h = C.c_void_p()
@@ -455,14 +482,14 @@ class EngineCore:
     def update_view(self, rgba, depth_mm):
         rgba = np.ascontiguousarray(rgba, dtype=np.uint8)
         depth_mm = np.ascontiguousarray(depth_mm, dtype=np.int16)
-        assert rgba.shape == (self.H, self.W, 4) and depth_mm.shape == (self.H, self.W)
+        assert rgba.shape == (self.Hr, self.Wr, 4) and depth_mm.shape == (self.H, self.W)
         self._check(self.api.update_view(self._h, _ptr(rgba), _ptr(depth_mm)))
 
     def update_view_bgr(self, bgr, depth_mm):
         """InfiniTamDriver::UpdateView from the host's own cv::Mat3b layout (packed BGR) + int16 mm: converted in the ingest kernel."""
         bgr = np.ascontiguousarray(bgr, dtype=np.uint8)
         depth_mm = np.ascontiguousarray(depth_mm, dtype=np.int16)
-        assert bgr.shape == (self.H, self.W, 3) and depth_mm.shape == (self.H, self.W)
+        assert bgr.shape == (self.Hr, self.Wr, 3) and depth_mm.shape == (self.H, self.W)
         self._check(self.api.update_view_bgr(self._h, _ptr(bgr), _ptr(depth_mm)))
 
     def update_view_dev(self, rgba_dev_ptr, depth_mm_dev_ptr):
@@ -471,14 +498,14 @@ class EngineCore:
     def set_view_float(self, rgba, depth_m):
         rgba = np.ascontiguousarray(rgba, dtype=np.uint8)
         depth_m = np.ascontiguousarray(depth_m, dtype=np.float32)
-        assert rgba.shape == (self.H, self.W, 4) and depth_m.shape == (self.H, self.W)
+        assert rgba.shape == (self.Hr, self.Wr, 4) and depth_m.shape == (self.H, self.W)
         self._check(self.api.set_view_float(self._h, _ptr(rgba), _ptr(depth_m)))
 
     def set_view_float_dev(self, rgba_dev_ptr, depth_m_dev_ptr):
         self._check(self.api.set_view_float_dev(self._h, C.c_void_p(rgba_dev_ptr), C.c_void_p(depth_m_dev_ptr)))
 
     def get_view(self):
-        rgba = np.empty((self.H, self.W, 4), np.uint8)
+        rgba = np.empty((self.Hr, self.Wr, 4), np.uint8)
         depth = np.empty((self.H, self.W), np.float32)
         self._check(self.api.get_view(self._h, _ptr(rgba), _ptr(depth)))
         return rgba, depth
@@ -646,7 +673,9 @@ class EngineCore:
 
     # -- rendering ----------------------------------------------------------
     def get_image(self, image_type, pose_m=None, intrinsics=None, want_rgba=True, want_depth=False):
-        rgba = np.zeros((self.H, self.W, 4), np.uint8) if want_rgba else None
+        # (the original colour frame has the colour camera's size; every other image the depth camera's)
+        rgb_shape = (self.Hr, self.Wr, 4) if int(image_type) == _capi.IMAGE_ORIGINAL_RGB else (self.H, self.W, 4)
+        rgba = np.zeros(rgb_shape, np.uint8) if want_rgba else None
         depth = np.zeros((self.H, self.W), np.float32) if want_depth else None
         pm = _colmajor(pose_m) if pose_m is not None else None
         intr = np.ascontiguousarray(intrinsics, dtype=np.float32) if intrinsics is not None else None
@@ -1387,6 +1416,7 @@ class InfiniTamDriver:
     """
 
     def __init__(self, settings, calib, voxel_decay_params=None, use_depth_weighting=False, api=None):
+        require_same_size(calib, "InfiniTamDriver")  # (DynSLAM's CreateItmCalib; its previews and silhouettes assume it)
         self.core = EngineCore(settings, calib, api=api)
         self.voxel_decay_params = voxel_decay_params or VoxelDecayParams(False, 0, 0)
         self.use_depth_weighting = bool(use_depth_weighting)

@@ -275,13 +275,27 @@ class ShardedScene:
         self.maps = bool(maps)
         assert not (self.maps and self.has_static), "map volumes: has_static=False (every volume is one)"
         self.owns_static = self.has_static and 0 in volumes_of_rank(rank, n_volumes, world_size, True)
-        self.static = make_engine("static") if self.owns_static else None
-        self.instances = {k: make_engine("map" if self.maps else "instance") for k in instances_of_rank(rank, n_volumes, world_size, self.has_static)}
+        from .engine import DsrError, require_same_size
+        made = []
+
+        def make_checked(kind):
+            # the view split, the layers and the composite move whole frames between colour and depth images: one size for both,
+            # checked on every engine as it arrives; a refusal closes what was made so far
+            eng = make_engine(kind)
+            made.append(eng)
+            try:
+                require_same_size(eng.calib, "ShardedScene")
+            except DsrError:
+                for m in made:
+                    m.close()
+                raise
+            return eng
+        self.static = make_checked("static") if self.owns_static else None
+        self.instances = {k: make_checked("map" if self.maps else "instance") for k in instances_of_rank(rank, n_volumes, world_size, self.has_static)}
         # the full frame the instance views are cut from
-        self.source = self.static if self.owns_static else (make_engine("view") if (self.instances and not self.maps) else None)
+        self.source = self.static if self.owns_static else (make_checked("view") if (self.instances and not self.maps) else None)
         # one instance volume next to its view engine on a GPU of their own (north_star's layout at 8 GPUs): ONE stream for the pair,
         # no cross-stream event in the frame (dsr_engine_share_stream)
-        from .engine import DsrError
         if self.on_gpu and share_streams and not self.owns_static and len(self.instances) == 1 and not self.maps:
             try:
                 next(iter(self.instances.values())).share_stream(self.source)

@@ -347,7 +347,9 @@ int dsr_decay(dsr_engine *e, int max_weight, int min_age, int force_all_voxels);
  * (InfiniTamDriver.cpp:178-183,202-207).  pose_m: world->camera of the free
  * camera (NULL: current pose_d); intrinsics: fx,fy,cx,cy (NULL: depth calib).
  * rgba_out (4*W*H bytes) and/or depth_out (W*H floats; metres, 0 = miss) are HOST
- * buffers; either may be NULL. */
+ * buffers; either may be NULL.
+ * DSR_IMAGE_ORIGINAL_RGB is the colour frame as given and has the COLOUR camera's size: rgba_out then
+ * takes 4 * calib.rgb.width * calib.rgb.height bytes (the same as 4*W*H wherever both cameras are one, as in DynSLAM). */
 int dsr_get_image(dsr_engine *e, int type, const float pose_m[16], const float intrinsics[4],
                   uint8_t *rgba_out, float *depth_out);
 /* Same, results left in caller-provided HBM buffers (for the multi-GPU

@@ -1486,7 +1486,7 @@ int orc_get_image(dsr_engine *h, int type, const float pose_m[16], const float i
   const size_t P = (size_t)E.W * E.H;
   switch (type) {
     case DSR_IMAGE_ORIGINAL_RGB:
-      if (rgba_out) memcpy(rgba_out, E.rgb.data(), P * 4);
+      if (rgba_out) memcpy(rgba_out, E.rgb.data(), (size_t)E.Wr * E.Hr * 4); /* the colour camera's size */
       return DSR_OK;
     case DSR_IMAGE_SCENERAYCAST:
       if (rgba_out) memcpy(rgba_out, E.live.raycastImage.data(), P * 4);
@@ -1691,7 +1691,7 @@ int orc_view_extract_silhouette(dsr_engine *m, dsr_engine *inst, const uint8_t *
   if (!m || !inst || !mask || box_w <= 0 || box_h <= 0) return fail(DSR_E_ARG, "bad silhouette arguments");
   Engine &src = m->e, &dst = inst->e;
   if (!src.hasView) return fail(DSR_E_NO_VIEW, "no view yet");
-  if (src.W != dst.W || src.H != dst.H || src.Wr != dst.Wr || src.Hr != dst.Hr || src.W != src.Wr) return fail(DSR_E_ARG, "size mismatch");
+  if (src.W != dst.W || src.H != dst.H || src.Wr != dst.Wr || src.Hr != dst.Hr || src.W != src.Wr || src.H != src.Hr) return fail(DSR_E_ARG, "size mismatch");
   const int frame_width = src.W, frame_height = src.H;
   memset(dst.rgb.data(), 255, (size_t)frame_width * frame_height * sizeof(V4u));
   memset(dst.depth.data(), 0, (size_t)frame_width * frame_height * sizeof(float));
@@ -1714,6 +1714,7 @@ int orc_view_extract_silhouette(dsr_engine *m, dsr_engine *inst, const uint8_t *
 int orc_view_remove_silhouette(dsr_engine *h, const uint8_t *mask, int x0, int y0, int box_w, int box_h) {
   if (!h || !mask || box_w <= 0 || box_h <= 0) return fail(DSR_E_ARG, "bad silhouette arguments");
   if (!E.hasView) return fail(DSR_E_NO_VIEW, "no view yet");
+  if (E.W != E.Wr || E.H != E.Hr) return fail(DSR_E_ARG, "rgb and depth sizes differ");
   for (int row = 0; row < box_h; ++row)
     for (int col = 0; col < box_w; ++col) {
       int frame_row = row + y0, frame_col = col + x0;
