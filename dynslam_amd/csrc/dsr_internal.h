@@ -20,6 +20,8 @@
 //   dsr_erase.hip     erase and crop: a volume cleared by oriented boxes or by another volume's surface (include/dsr_erase.h): the checks,
 //                     the candidates, the one launch of k_erase.h, then the voxel GC's own commit and compaction; and the same by a
 //                     per-point mask on a dense grid (dsr_erase_by_mask of include/dsr_components.h)
+//   dsr_points.hip    a range sensor's sweep fused into a volume (include/dsr_points.h): enumerate, sort + unique, the merge's ordered
+//                     insert, accumulate, fold
 //   dsr_components.hip connected components of a dense grid and despeckle (include/dsr_components.h): the launches of
 //                     k_components.h around one scan; dsr_despeckle = export, label, erase by mask
 // The units from dsr_merge.hip's dense grids down share their host-side scaffolding through dsr_hostcall.h (host code only: any unit
@@ -27,7 +29,7 @@
 // of a call's host planes, the uploads, the copies back with the counters among them, the ONE host wait.  Each unit keeps what
 // differs: its own checks and their order, its *_queue (the launches) and its *_fill_result (what the counters mean).
 // Every KERNEL header (k_*.h) is included by exactly ONE of them: __global__ kernels have external linkage.  Headers that hold only
-// inline device functions (dsr_device.h, dsr_math.h, dsr_sample.h, k_dense_sample.h) are shared: any unit may include them.
+// inline device functions (dsr_device.h, dsr_math.h, dsr_sample.h, dsr_insert.h, k_dense_sample.h) are shared: any unit may include them.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -45,6 +47,7 @@
 #include <vector>
 
 #include "dsr_device.h"
+#include "dsr_insert.h"
 #include "../../include/dsr_mesh.h"
 #include "../../include/dsr_track.h"
 
@@ -54,6 +57,7 @@ struct dsr_dense_grid;           // include/dsr_dense.h
 struct dsr_erase_params;         // include/dsr_erase.h
 namespace dsr { struct DenseP; } // k_dense_sample.h
 namespace dsr { struct EraseRes; } // k_erase.h
+namespace dsr { struct MergeP; }   // k_merge.h
 
 namespace dsr_internal {
 std::string &last_error();  // thread-local message behind dsr_last_error() (dsr_engine.hip)
@@ -447,6 +451,31 @@ inline bool rigid_transform(const float *m) {
     }
   return true;
 }
+// ---- dsr_merge.hip: the ordered insert of include/dsr_merge.h steps 3 and 4 (kernels: k_merge.h), for the calls that allocate the
+// blocks a volume lacks in that order: the merge, the dense import, the point-cloud fusion (dsr_points.hip).
+// InsertScratch: what such a call allocates for its N candidate blocks (freed when it leaves): per candidate the key and the bucket
+// (A: as the passes write them, B: sorted by the insert), info (k_merge.h has_data_body), the insert's plan .. blockRank; the result
+// words (MR_*) with the number of unique keys behind them, the voxel counter; hipCUB's temporary storage, large enough for every
+// hipCUB call of ordered_insert and — withSort — for a sort + unique of the keys.
+struct InsertScratch {
+  Scratch sc;
+  unsigned long long *keysA, *keysB, *voxels;
+  uint32_t *bucketsA, *bucketsB;
+  int32_t *info, *exc, *excRank, *consumes, *blockRank, *res, *nUnique;
+  int2 *plan;
+  uint8_t *tmp;
+  size_t tmpBytes = 0;
+  explicit InsertScratch(const char *what) : sc(what) {}
+  int init(int N, bool withSort, hipStream_t stream);
+};
+// ... the insert of the candidates dst lacks, queued on dst's stream.  bucketsA / keysA: per candidate its bucket (kMergeNoBucket:
+// nothing to insert) and key; m: the dst fields — the second form fills them from dst itself
+int ordered_insert(dsr_engine *dst, const dsr::MergeP &m, int N, const InsertScratch &s);
+int ordered_insert(dsr_engine *dst, int N, const InsertScratch &s);
+// ... the tail of such a call, after its last launch: e's map has changed — the free-view cache and the cached list of allocated
+// entries are stale —; then a host wait, for the result words and the voxel count
+struct InsertOutcome { int32_t res[MR_COUNT]; unsigned long long voxels; int dropped; };
+int insert_read_back(dsr_engine *e, const InsertScratch &s, InsertOutcome &o);
 // what such a call asks of its two engines and of the transform m (named mName in the message) between them; w: "merge" / "align"
 inline int two_volume_check(const dsr_engine *dst, const dsr_engine *src, const float *m, const char *what, const char *mName) {
   const std::string w(what);

@@ -31,43 +31,33 @@ int boxes_per_axis(const float *m, int row, double vsSrc, double vsDst) {
   return (int)std::floor(ext / 8.0) + 2;
 }
 
-// What a call that pulls data into a volume allocates for its N candidate blocks (freed when it leaves): per candidate the key and
-// the bucket (A: as the passes write them, B: sorted by the insert), info (k_merge.h has_data_body), the insert's plan .. blockRank;
-// the result words (MR_*) with the number of unique keys behind them, the voxel counter; hipCUB's temporary storage, large
-// enough for every hipCUB call of ordered_insert and — withSort — for the merge's sort + unique of the keys.
-struct InsertScratch {
-  Scratch sc;
-  unsigned long long *keysA, *keysB, *voxels;
-  uint32_t *bucketsA, *bucketsB;
-  int32_t *info, *exc, *excRank, *consumes, *blockRank, *res, *nUnique;
-  int2 *plan;
-  uint8_t *tmp;
-  size_t tmpBytes = 0;
-  explicit InsertScratch(const char *what) : sc(what) {}
-  int init(int N, bool withSort, hipStream_t stream) {
-    int st;
-    if ((st = sc.get(&keysA, N)) || (st = sc.get(&keysB, N)) || (st = sc.get(&bucketsA, N)) || (st = sc.get(&bucketsB, N)) ||
-        (st = sc.get(&info, N)) || (st = sc.get(&exc, N)) || (st = sc.get(&excRank, N)) || (st = sc.get(&consumes, N)) ||
-        (st = sc.get(&blockRank, N)) || (st = sc.get(&plan, N)) || (st = sc.get(&res, MR_COUNT + 1)) || (st = sc.get(&voxels, 1)))
-      return st;
-    nUnique = res + MR_COUNT;
-    size_t b = 0;
-    if (withSort) {
-      HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, b, keysA, keysB, N, 0, 49, stream)); tmpBytes = std::max(tmpBytes, b);
-      HIP_TRY(hipcub::DeviceSelect::Unique(nullptr, b, keysB, keysA, nUnique, N, stream)); tmpBytes = std::max(tmpBytes, b);
-    }
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, b, bucketsA, bucketsB, keysA, keysB, N, 0, 32, stream)); tmpBytes = std::max(tmpBytes, b);
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, b, exc, excRank, N, stream)); tmpBytes = std::max(tmpBytes, b);
-    if ((st = sc.get(&tmp, tmpBytes))) return st;
-    HIP_TRY(hipMemsetAsync(voxels, 0, sizeof *voxels, stream));
-    return DSR_OK;
+}  // namespace
+
+// InsertScratch (dsr_internal.h): what a call that pulls data into a volume allocates for its N candidate blocks
+int dsr_internal::InsertScratch::init(int N, bool withSort, hipStream_t stream) {
+  int st;
+  if ((st = sc.get(&keysA, N)) || (st = sc.get(&keysB, N)) || (st = sc.get(&bucketsA, N)) || (st = sc.get(&bucketsB, N)) ||
+      (st = sc.get(&info, N)) || (st = sc.get(&exc, N)) || (st = sc.get(&excRank, N)) || (st = sc.get(&consumes, N)) ||
+      (st = sc.get(&blockRank, N)) || (st = sc.get(&plan, N)) || (st = sc.get(&res, MR_COUNT + 1)) || (st = sc.get(&voxels, 1)))
+    return st;
+  nUnique = res + MR_COUNT;
+  size_t b = 0;
+  if (withSort) {
+    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, b, keysA, keysB, N, 0, 49, stream)); tmpBytes = std::max(tmpBytes, b);
+    HIP_TRY(hipcub::DeviceSelect::Unique(nullptr, b, keysB, keysA, nUnique, N, stream)); tmpBytes = std::max(tmpBytes, b);
   }
-};
+  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, b, bucketsA, bucketsB, keysA, keysB, N, 0, 32, stream)); tmpBytes = std::max(tmpBytes, b);
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, b, exc, excRank, N, stream)); tmpBytes = std::max(tmpBytes, b);
+  if ((st = sc.get(&tmp, tmpBytes))) return st;
+  HIP_TRY(hipMemsetAsync(voxels, 0, sizeof *voxels, stream));
+  return DSR_OK;
+}
+
 
 // The ordered insert of the candidates dst lacks (dsr_merge.h step 3), queued on dst's stream: a stable sort by bucket (the key
 // order survives inside a bucket), plan, two exclusive sums, apply, finish.  bucketsA / keysA: per candidate its bucket
 // (kMergeNoBucket: nothing to insert) and key; m: the dst fields.
-int ordered_insert(dsr_engine *dst, const MergeP &m, int N, const InsertScratch &s) {
+int dsr_internal::ordered_insert(dsr_engine *dst, const MergeP &m, int N, const InsertScratch &s) {
   ProfScope ps(dst, "merge_alloc");
   size_t b = s.tmpBytes;
   HIP_TRY(hipcub::DeviceRadixSort::SortPairs(s.tmp, b, s.bucketsA, s.bucketsB, s.keysA, s.keysB, N, 0, 32, dst->stream));
@@ -84,10 +74,16 @@ int ordered_insert(dsr_engine *dst, const MergeP &m, int N, const InsertScratch 
   return DSR_OK;
 }
 
+// ... with m's dst fields taken from dst itself (the callers that have no MergeP of their own: dsr_points.hip)
+int dsr_internal::ordered_insert(dsr_engine *dst, int N, const InsertScratch &s) {
+  MergeP m{};
+  m.dstBuckets = dst->noBuckets; m.dstEntries = dst->E; m.dstBlocks = dst->noBlocks; m.dstMask = (uint32_t)(dst->noBuckets - 1);
+  return ordered_insert(dst, m, N, s);
+}
+
 // The tail of such a call, after its last launch: e's map has changed — the free-view cache and the cached list of allocated
 // entries are stale —; then the ONE host wait, for the result words and the voxel count.
-struct InsertOutcome { int32_t res[MR_COUNT]; unsigned long long voxels; int dropped; };
-int insert_read_back(dsr_engine *e, const InsertScratch &s, InsertOutcome &o) {
+int dsr_internal::insert_read_back(dsr_engine *e, const InsertScratch &s, InsertOutcome &o) {
   HIP_TRY(hipGetLastError());
   e->sceneVersion++;
   e->allocListVersion = ~0ull;
@@ -98,8 +94,6 @@ int insert_read_back(dsr_engine *e, const InsertScratch &s, InsertOutcome &o) {
   o.dropped = o.res[MR_NEEDED] - o.res[MR_ALLOCATED];
   return DSR_OK;
 }
-
-}  // namespace
 
 extern "C" {
 

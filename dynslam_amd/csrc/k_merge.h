@@ -11,18 +11,10 @@
 // shared (dsr_sample.h), combineVoxel*Information too (dsr_device.h).  The has-data and the pull pass are written once, over a
 // SOURCE of samples: the volume here, a dense grid's planes in k_dense.h.
 #pragma once
+#include "dsr_insert.h"  // the packed keys, the sentinels, the result words (MR_*): shared with the insert's other callers
 #include "dsr_sample.h"
 
 namespace dsr {
-
-constexpr unsigned long long kMergeNoKey = 1ull << 48;   // sorts behind every packed position
-constexpr unsigned long long kMergeKeyMask = (1ull << 48) - 1;
-constexpr uint32_t kMergeNoBucket = 0xffffffffu;
-
-enum MergeRes {  // the device-side result words
-  MR_CANDIDATES = 0, MR_WITH_DATA = 1, MR_ALLOCATED = 2, MR_NEEDED = 3, MR_ALLOCATED_EXCESS = 4, MR_SRC_ENTRIES = 5, MR_UNIQUE = 6,
-  MR_OLD_V = 7, MR_OLD_E = 8, MR_COUNT = 16
-};
 
 struct MergeP {
   Mat4 srcToDst, dstToSrc;
@@ -34,17 +26,6 @@ struct MergeP {
   int nx, ny, nz;  // candidate box per src entry (blocks per axis), nx * ny * nz keys
   int capacity;    // keys in the candidate arrays
 };
-
-// the stored key DESCENDS with the packed position (dsr_merge.h step 3): an ascending sort yields the insert order
-__host__ __device__ __forceinline__ unsigned long long merge_key(int bx, int by, int bz) {
-  const unsigned long long packed = (unsigned long long)(uint32_t)(bx + 32768) | ((unsigned long long)(uint32_t)(by + 32768) << 16) |
-                                    ((unsigned long long)(uint32_t)(bz + 32768) << 32);
-  return kMergeKeyMask - packed;
-}
-__host__ __device__ __forceinline__ void merge_unkey(unsigned long long key, int &bx, int &by, int &bz) {
-  const unsigned long long packed = kMergeKeyMask - key;
-  bx = (int)(packed & 0xffffu) - 32768; by = (int)((packed >> 16) & 0xffffu) - 32768; bz = (int)((packed >> 32) & 0xffffu) - 32768;
-}
 
 // ------------------------------------------------------------------ candidates
 

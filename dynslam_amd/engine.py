@@ -901,6 +901,15 @@ class EngineCore:
             raise
         return out
 
+    # ---- a range sensor's sweep fused into the volume (include/dsr_points.h; builder-defined)
+    def fuse_points(self, points, sensor_to_world=None, min_range=0.5, max_range=80.0, hit_weight=1):
+        """Integrate the returns `points` — (n, 3) or (n, 4) float32 in the sensor's frame, a numpy array or a contiguous torch tensor
+        on the engine's GPU (the tensor LidarEvaluator takes) — at the rigid pose sensor_to_world (4x4 row-major; None: identity;
+        dynslam_amd.points.sensor_pose makes it from KITTI's calibration) — dsr_fuse_points.  Returns the counts as a dict; raises
+        OutOfBlocksError, with the dict as its `result`, when the engine ran out of blocks (what fitted is kept)."""
+        from . import points as _points
+        return _points.fuse_points(self, points, sensor_to_world, min_range, max_range, hit_weight)
+
     # ---- erase and crop (include/dsr_erase.h, DESIGN.md §23; builder-defined)
     def _erase_api(self):
         return optional_api(self.api, "erase")
@@ -1533,6 +1542,12 @@ class InfiniTamDriver:
         the rigid transform src_to_dst (other's world -> this world) — what a host calls before it frees a pruned track's
         reconstruction.  Returns the merge result as a dict."""
         return self.core.merge_from(other.core, src_to_dst)
+
+    def FusePoints(self, points, sensor_to_world=None, **kwargs):
+        """ITMMainEngine::FusePoints (builder-defined, include/dsr_points.h): a range sensor's sweep — KITTI's Velodyne records, the
+        array the LIDAR evaluation takes — integrated into the volume at the sensor's pose.  Returns EngineCore.fuse_points's dict
+        of counts; raises OutOfBlocksError on exhaustion like Integrate (INTEGRATION.md "range-sensor sweeps")."""
+        return self.core.fuse_points(points, sensor_to_world, **kwargs)
 
     def ExportDense(self, shape, pitch, grid_to_world=None, **kwargs):
         """ITMMainEngine::ExportDense (builder-defined, include/dsr_dense.h): the volume sampled on a regular lattice —

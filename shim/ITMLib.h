@@ -35,6 +35,7 @@
 #include "../include/dsr_heightmap.h"
 #include "../include/dsr_erase.h"
 #include "../include/dsr_components.h"
+#include "../include/dsr_points.h"
 
 // The tracker's entry points are referenced WEAKLY: a host linked against a library without them (the CPU oracle's orc_* build
 // of the reference's hosts) still links, and ITMTrackingController::Track then throws as it did before the tracker existed.
@@ -59,6 +60,10 @@ int dsr_save_scene_to_mesh_indexed(dsr_engine *e, const char *path, int flags) _
 // ... and the volume merge's (include/dsr_merge.h): MergeFrom throws on a library without it
 int dsr_merge_volume(dsr_engine *dst, dsr_engine *src, const float src_to_dst_m[16], const dsr_merge_params *params,
                      dsr_merge_result *result) __attribute__((weak));
+// ... and the point-cloud fusion's (include/dsr_points.h): FusePoints throws on a library without it
+int dsr_fuse_points(dsr_engine *e, int64_t n, const float *points, const float sensor_to_world_m[16], const dsr_points_params *params,
+                    dsr_points_result *result) __attribute__((weak));
+void dsr_points_default_params(dsr_points_params *p) __attribute__((weak));
 // ... and the dense grids' (include/dsr_dense.h): ExportDense / ImportDense throw on a library without them
 int dsr_dense_export(dsr_engine *e, const dsr_dense_grid *grid, float *sdf, uint8_t *w_depth, uint8_t *rgba, dsr_dense_result *result) __attribute__((weak));
 int dsr_dense_import(dsr_engine *e, const dsr_dense_grid *grid, const float *sdf, const uint8_t *w_depth, const uint8_t *rgba,
@@ -693,6 +698,21 @@ class ITMMainEngine {
     dsr_merge_result res;
     memset(&res, 0, sizeof res);
     ITMLib::Engine::dsr_throw(dsr_merge_volume(engine_, other.engine_, src_to_dst.m, nullptr, &res));
+    return res;
+  }
+  // BUILDER-DEFINED (include/dsr_points.h): a range sensor's sweep — n records of `stride` floats (3: x y z; 4: KITTI's
+  // x y z reflectance) in the sensor's frame — integrated into this volume at the rigid pose sensor_to_world (metres of the sensor's
+  // frame -> metres of this volume's world), allocating what the volume lacks.  Throws on exhaustion like Integrate (what fitted is kept).
+  dsr_points_result FusePoints(const float *points, int64_t n, const Matrix4f &sensor_to_world, int stride = 4,
+                               const dsr_points_params *params = nullptr) {
+    if (!dsr_fuse_points || !dsr_points_default_params) throw std::runtime_error("this library has no point-cloud fusion (include/dsr_points.h)");
+    dsr_points_params prm;
+    dsr_points_default_params(&prm);
+    if (params) prm = *params;
+    else prm.stride = stride;
+    dsr_points_result res;
+    memset(&res, 0, sizeof res);
+    ITMLib::Engine::dsr_throw(dsr_fuse_points(engine_, n, points, sensor_to_world.m, &prm, &res));
     return res;
   }
   // BUILDER-DEFINED (include/dsr_erase.h): the voxels inside the union of n oriented boxes cleared (EraseBoxes), the
